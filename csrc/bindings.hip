@@ -48,6 +48,9 @@ __global__ void topk_scan_fp4_v3_kernel(const uint8_t*, const uint8_t*, const ui
 __global__ void topk_scan_fp4_v5_kernel(const uint8_t*, const uint8_t*, const uint8_t*,
                                         const uint8_t*, int, int, int, int, int,
                                         float*, int32_t*, const float*, int32_t*, int);
+__global__ void topk_scan_fp4_v7_kernel(const uint8_t*, const uint8_t*, const uint8_t*,
+                                        const uint8_t*, int, int, int, int, int,
+                                        float*, int32_t*, const float*, int32_t*, int);
 
 
 __global__ void topk_merge_kernel(const float*, const int32_t*, int, int, int,
@@ -371,8 +374,12 @@ torch::Tensor audit_pack(torch::Tensor verdict, torch::Tensor risk, torch::Tenso
 
 std::vector<torch::Tensor> topk_scan_threshold_fp4x4(
     torch::Tensor Q4, torch::Tensor QS, torch::Tensor X4, torch::Tensor XS,
-    torch::Tensor theta, int64_t cap, int64_t n_swaths) {
-  // both operands MXFP4 (csrc topk_scan_fp4_kernel); scores at x1
+    torch::Tensor theta, int64_t cap, int64_t n_swaths, int64_t variant_arg,
+    bool scan_only) {
+  // both operands MXFP4 (csrc topk_scan_fp4_kernel); scores at x1.
+  // variant_arg: -1 = environment/default, 0 = v1, 1 = v2, 2 = v3,
+  // 4 = v5, 7 = v7. scan_only runs the K-loops without the epilogue
+  // (k = -1) for epilogue-share attribution.
   CHECK_GPU(Q4); CHECK_CONTIG(Q4); CHECK_GPU(QS); CHECK_CONTIG(QS);
   CHECK_GPU(X4); CHECK_CONTIG(X4); CHECK_GPU(XS); CHECK_CONTIG(XS);
   CHECK_GPU(theta); CHECK_CONTIG(theta);
@@ -382,14 +389,20 @@ std::vector<torch::Tensor> topk_scan_threshold_fp4x4(
   TORCH_CHECK(QS.size(0) == nq && QS.size(1) == D / 32);
   TORCH_CHECK(X4.size(1) == D / 2 && XS.size(0) == nx && XS.size(1) == D / 32);
   TORCH_CHECK(theta.numel() == nq && cap >= 32 && cap <= 4096);
-  // v3 (2-pair barrier intervals) is the default: bit-exact vs v1 and
-  // measured 15.4 vs 16.4 ms at 4.2M x 4096. Env overrides for A/B.
-  static const int variant = [] {
+  // v7 (v3 + wave any-hit fast path, hoisted staging addresses, Q scale
+  // sheet staged once) is the default: bit-exact vs v1 and measured 11.0
+  // vs 15.4 ms at 4.2M x 4096. Env overrides for A/B.
+  static const int env_variant = [] {
     if (const char* e = getenv("VAINPLEX_FP4_V1"); e && e[0] == '1') return 0;
     if (const char* e = getenv("VAINPLEX_FP4_V2"); e && e[0] == '1') return 1;
+    if (const char* e = getenv("VAINPLEX_FP4_V3"); e && e[0] == '1') return 2;
     if (const char* e = getenv("VAINPLEX_FP4_V5"); e && e[0] == '1') return 4;
-    return 2;
+    return 7;
   }();
+  int variant = variant_arg < 0 ? env_variant : (int)variant_arg;
+  TORCH_CHECK(variant == 0 || variant == 1 || variant == 2 || variant == 4 ||
+              variant == 7,
+              "fp4x4 scan: unknown variant ", variant);
   int n_qblocks = (nq + 255) / 256;
   if (n_swaths <= 0) {
     int want = 256 / (n_qblocks > 0 ? n_qblocks : 1);
@@ -403,13 +416,14 @@ std::vector<torch::Tensor> topk_scan_threshold_fp4x4(
   auto cand_i = torch::full({(long long)nq, cap}, -1, i32opts);
   auto counts = torch::zeros({(long long)nq}, i32opts);
   dim3 grid((unsigned)(n_qblocks * n_swaths));
-  auto kern = variant == 4 ? topk_scan_fp4_v5_kernel
+  auto kern = variant == 7 ? topk_scan_fp4_v7_kernel
+            : variant == 4 ? topk_scan_fp4_v5_kernel
             : variant == 2 ? topk_scan_fp4_v3_kernel
             : variant == 1 ? topk_scan_fp4_v2_kernel : topk_scan_fp4_kernel;
   hipLaunchKernelGGL(kern, grid, dim3(512), 0, cur_stream(),
                      Q4.data_ptr<uint8_t>(), QS.data_ptr<uint8_t>(),
                      X4.data_ptr<uint8_t>(), XS.data_ptr<uint8_t>(),
-                     nq, (int)nx, D, 1, (int)n_swaths,
+                     nq, (int)nx, D, scan_only ? -1 : 1, (int)n_swaths,
                      cand_s.data_ptr<float>(), cand_i.data_ptr<int32_t>(),
                      theta.data_ptr<float>(), counts.data_ptr<int32_t>(),
                      (int)cap);
@@ -562,7 +576,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return std::vector<torch::Tensor>{cand_s, cand_i, counts};
   }, "MXFP4-X threshold scan");
   m.def("topk_scan_threshold_fp4x4", &topk_scan_threshold_fp4x4,
-        "full-MXFP4 threshold scan (both operands e2m1 + e8m0 group scales)");
+        "full-MXFP4 threshold scan (both operands e2m1 + e8m0 group scales)",
+        py::arg("Q4"), py::arg("QS"), py::arg("X4"), py::arg("XS"),
+        py::arg("theta"), py::arg("cap"), py::arg("n_swaths"),
+        py::arg("variant") = -1, py::arg("scan_only") = false);
   m.def("edit_distance", [](torch::Tensor bytes, torch::Tensor offsets) {
     // batched Levenshtein over string PAIRS: offsets has 2*n+1 entries;
     // pair i = strings (2i, 2i+1) in the packed byte buffer

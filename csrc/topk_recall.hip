@@ -1667,6 +1667,275 @@ topk_scan_fp4_v3_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
 
 
 // ===========================================================================
+// fp4x4 threshold scan v7: v3's tile geometry, LDS image, 2-pair
+// intervals, fragment reads and MFMA body, with the per-tile work around
+// the K-loop cut down:
+//  - any-hit fast path: the lane's 32 thresholds come in as 8
+//    ds_read_b128 (rows wm*128 + m*16 + (lane>>4)*4 + r are contiguous in
+//    r), max over n per (m, r), one wave-uniform branch on the ballot. A
+//    wave with no score above its thresholds (>90 % of wave-tiles at
+//    production theta) skips the 128-element compare/append loop. The
+//    loop itself is v3's, so the hit condition stays exactly v > theta and
+//    clamped rows/columns of ragged tiles are still filtered there.
+//  - hoisted staging addresses: a lane stages the same two rows of every
+//    pair, so its two byte offsets (clamped row * ld + swizzled slot) are
+//    computed once per block for Q and once per tile for X; each glds is
+//    then wave-uniform 64-bit base (row0*ld + pair*64) + 32-bit lane
+//    offset. Offsets span at most 256 rows * 512 B; the base carries the
+//    index size.
+//  - the Q scale sheet is identical for the whole block: staged once in
+//    the block prologue instead of once per tile. The first tile's
+//    interval-0 vmcnt(0) + barrier orders it before its first reader.
+// The per-row candidate-pointer arithmetic (grow * cap, 64-bit) lives in
+// the slow path only; with it out of the block-lifetime registers the
+// kernel holds no scratch at all (v3: 41 VGPR + 20 SGPR spills).
+// Tile boundary: as in v3 the trailing barrier orders every wave's last
+// fragment/scale reads (each asm read block ends in lgkmcnt(0)) before
+// the next tile's head restages pair buffers 0,1 and the X scale sheet —
+// for np <= 2 those are the very buffers the last interval read. Issuing
+// that head BEFORE the epilogue (so it flies under it) was measured and
+// taken out: with the fast path the epilogue is too short to hide
+// anything and the scan got 3 % slower (profiles/README.md).
+// ===========================================================================
+
+// byte offsets of the two 16 B pieces a lane stages per pair tile
+// ([256 rows][4 slots], piece = w*64 + i*512 + lane), rows clamped to
+// the tile's live rows (garbage rows are filtered in the epilogue)
+DEVINL void stage_row_offsets(uint32_t w, uint32_t lane, uint32_t rows_live,
+                              uint32_t ld_bytes, uint32_t off[2]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    uint32_t piece = w * WAVE + i * TK_THREADS + lane;
+    uint32_t r = piece >> 2;
+    uint32_t slot = piece & 3;
+    uint32_t src_slot = slot ^ ((r >> 2u) & 3u);
+    if (r >= rows_live) r = rows_live - 1;
+    off[i] = r * ld_bytes + src_slot * 16u;
+  }
+}
+
+// stage one pair tile: base is wave-uniform (tile row0 * ld + pair * 64)
+DEVINL void stage_tile_off(const uint8_t* __restrict__ base,
+                           const uint32_t off[2], bf16* lds_base, uint32_t w) {
+  auto ldst = (AS3 char*)lds_base + w * (WAVE * 16);
+  __builtin_amdgcn_global_load_lds((const AS1 void*)(base + off[0]),
+                                   (AS3 void*)ldst, 16, 0, 0);
+  __builtin_amdgcn_global_load_lds((const AS1 void*)(base + off[1]),
+                                   (AS3 void*)(ldst + TK_THREADS * 16), 16, 0, 0);
+}
+
+extern "C" __global__ void __launch_bounds__(TK_THREADS)
+topk_scan_fp4_v7_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restrict__ QS,
+                        const uint8_t* __restrict__ X4, const uint8_t* __restrict__ XS,
+                        int nq, int nx, int D, int k, int n_swaths,
+                        float* __restrict__ cand_scores,
+                        int32_t* __restrict__ cand_ids,
+                        const float* __restrict__ theta,
+                        int32_t* __restrict__ tc_n, int cap) {
+  __shared__ bf16 lds_q[4 * BM * BK];
+  __shared__ bf16 lds_x[4 * BN * BK];
+  __shared__ uint8_t lds_qs[BM * 32];
+  __shared__ uint8_t lds_xs2[BN * 32];
+  __shared__ __attribute__((aligned(16))) float row_min[BM];
+#define QP4E(buf) (lds_q + (buf) * BM * BK)
+#define XP4E(buf) (lds_x + (buf) * BN * BK)
+
+  int S = n_swaths;
+  int qb = blockIdx.x / S;
+  int swath = blockIdx.x % S;
+  long long row0 = (long long)qb * BM;
+
+  long long per = ((long long)nx + S - 1) / S;
+  per = ((per + BN - 1) / BN) * BN;
+  long long x_begin = (long long)swath * per;
+  long long x_end = min((long long)nx, x_begin + per);
+  if (x_begin >= x_end) return;
+
+  for (int i = threadIdx.x; i < BM; i += blockDim.x)
+    row_min[i] = (theta != nullptr && row0 + i < nq) ? theta[row0 + i] : -1e30f;
+  __syncthreads();
+
+  int wid = wave_id();
+  uint32_t wu = (uint32_t)__builtin_amdgcn_readfirstlane(wid);
+  int wm = wid >> 2, wn = wid & 3;
+  int lane = lane_id();
+  int lrow = lane & 15;
+  int kgrp = lane >> 4;
+  int np = D / (2 * BK_F8);
+  int sb = D / 32;
+  uint32_t ldb = (uint32_t)(D / 2);  // row pitch in bytes
+
+  uint32_t qoff[2], xoff[2];
+  const uint8_t* qbase = Q4 + row0 * (long long)ldb;
+  stage_row_offsets(wu, (uint32_t)lane, (uint32_t)min((long long)BM, nq - row0),
+                    ldb, qoff);
+
+  // stage pair s of the Q block and of x tile xt into buffer s & 3
+  auto stage_pair = [&](long long xt, int s) {
+    stage_tile_off(qbase + s * 64, qoff, QP4E(s & 3), wu);
+    stage_tile_off(X4 + xt * (long long)ldb + s * 64, xoff, XP4E(s & 3), wu);
+  };
+  // x tile xt's scale sheet + first interval
+  auto stage_head = [&](long long xt) {
+    stage_row_offsets(wu, (uint32_t)lane, (uint32_t)min((long long)BN, nx - xt),
+                      ldb, xoff);
+    stage_scale_rows(XS, sb, xt, (long long)nx, lds_xs2, BN);
+    stage_pair(xt, 0);
+    if (np > 1) stage_pair(xt, 1);
+  };
+
+  stage_scale_rows(QS, sb, row0, (long long)nq, lds_qs, BM);
+
+  for (long long x0 = x_begin; x0 < x_end; x0 += BN) {
+    f32x4 acc[8][4] = {};
+    stage_head(x0);
+    for (int p = 0; p < np; p += 2) {
+      int pe = min(p + 2, np);
+      // all outstanding glds are exactly this interval's pairs (plus,
+      // at p == 0, the tile's X scale sheet and once the Q scale sheet)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      // stage the NEXT interval (pairs p+2, p+3) into the buffers the
+      // PREVIOUS interval consumed; overlaps this interval's compute
+      if (p + 2 < np) stage_pair(x0, p + 2);
+      if (p + 3 < np) stage_pair(x0, p + 3);
+      for (int pc = p; pc < pe; ++pc) {
+        uint32_t xrow_base = (uint32_t)(wn * 64 + lrow);
+        uint32_t qrow_base = (uint32_t)(wm * 128 + lrow);
+        uint32_t xaddr = (uint32_t)(size_t)XP4E(pc & 3)
+                         + lds_off_bytes(xrow_base, (uint32_t)kgrp);
+        uint32_t qaddr = (uint32_t)(size_t)QP4E(pc & 3)
+                         + lds_off_bytes(qrow_base, (uint32_t)kgrp);
+        uint32_t sst = 16u * (uint32_t)sb;
+        uint32_t xs_a = (uint32_t)(size_t)lds_xs2 + xrow_base * (uint32_t)sb
+                        + (uint32_t)(pc * 4 + kgrp);
+        uint32_t qs_a = (uint32_t)(size_t)lds_qs + qrow_base * (uint32_t)sb
+                        + (uint32_t)(pc * 4 + kgrp);
+        bf16x8 xf[4], qf[8];
+        uint32_t xs_v[4], qs_v[8];
+        asm volatile(
+            "ds_read_b128 %0, %8\n\t"
+            "ds_read_b128 %1, %8 offset:1024\n\t"
+            "ds_read_b128 %2, %8 offset:2048\n\t"
+            "ds_read_b128 %3, %8 offset:3072\n\t"
+            "ds_read_u8 %4, %9\n\t"
+            "ds_read_u8 %5, %10\n\t"
+            "ds_read_u8 %6, %11\n\t"
+            "ds_read_u8 %7, %12\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(xf[0]), "=&v"(xf[1]), "=&v"(xf[2]), "=&v"(xf[3]),
+              "=&v"(xs_v[0]), "=&v"(xs_v[1]), "=&v"(xs_v[2]), "=&v"(xs_v[3])
+            : "v"(xaddr), "v"(xs_a), "v"(xs_a + sst), "v"(xs_a + 2 * sst),
+              "v"(xs_a + 3 * sst));
+        asm volatile(
+            "ds_read_b128 %0, %16\n\t"
+            "ds_read_b128 %1, %16 offset:1024\n\t"
+            "ds_read_b128 %2, %16 offset:2048\n\t"
+            "ds_read_b128 %3, %16 offset:3072\n\t"
+            "ds_read_b128 %4, %16 offset:4096\n\t"
+            "ds_read_b128 %5, %16 offset:5120\n\t"
+            "ds_read_b128 %6, %16 offset:6144\n\t"
+            "ds_read_b128 %7, %16 offset:7168\n\t"
+            "ds_read_u8 %8, %17\n\t"
+            "ds_read_u8 %9, %18\n\t"
+            "ds_read_u8 %10, %19\n\t"
+            "ds_read_u8 %11, %20\n\t"
+            "ds_read_u8 %12, %21\n\t"
+            "ds_read_u8 %13, %22\n\t"
+            "ds_read_u8 %14, %23\n\t"
+            "ds_read_u8 %15, %24\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(qf[0]), "=&v"(qf[1]), "=&v"(qf[2]), "=&v"(qf[3]),
+              "=&v"(qf[4]), "=&v"(qf[5]), "=&v"(qf[6]), "=&v"(qf[7]),
+              "=&v"(qs_v[0]), "=&v"(qs_v[1]), "=&v"(qs_v[2]), "=&v"(qs_v[3]),
+              "=&v"(qs_v[4]), "=&v"(qs_v[5]), "=&v"(qs_v[6]), "=&v"(qs_v[7])
+            : "v"(qaddr), "v"(qs_a), "v"(qs_a + sst), "v"(qs_a + 2 * sst),
+              "v"(qs_a + 3 * sst), "v"(qs_a + 4 * sst), "v"(qs_a + 5 * sst),
+              "v"(qs_a + 6 * sst), "v"(qs_a + 7 * sst));
+        v8i_mx xv[4], qv[8];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) xv[n] = fp4_frag(xf[n]);
+#pragma unroll
+        for (int m = 0; m < 8; ++m) qv[m] = fp4_frag(qf[m]);
+#pragma unroll
+        for (int m = 0; m < 8; ++m)
+#pragma unroll
+          for (int n = 0; n < 4; ++n)
+            acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+                qv[m], xv[n], acc[m][n], 4 /*A fp4*/, 4 /*B fp4*/,
+                0, (int)qs_v[m], 0, (int)xs_v[n]);
+      }
+    }
+    // nothing is in flight here (the last interval staged nothing); the
+    // barrier orders every wave's last fragment reads before the next
+    // tile's head overwrites buffers 0,1 and the X scale sheet
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    // the lane's 32 thresholds, th[m][r] = row_min[wm*128 + m*16 +
+    // (lane>>4)*4 + r]
+    f32x4 th[8];
+    {
+      uint32_t ta = (uint32_t)(size_t)row_min
+                    + (uint32_t)(wm * 128 + (lane >> 4) * 4) * 4u;
+      asm volatile(
+          "ds_read_b128 %0, %8\n\t"
+          "ds_read_b128 %1, %8 offset:64\n\t"
+          "ds_read_b128 %2, %8 offset:128\n\t"
+          "ds_read_b128 %3, %8 offset:192\n\t"
+          "ds_read_b128 %4, %8 offset:256\n\t"
+          "ds_read_b128 %5, %8 offset:320\n\t"
+          "ds_read_b128 %6, %8 offset:384\n\t"
+          "ds_read_b128 %7, %8 offset:448\n\t"
+          "s_waitcnt lgkmcnt(0)"
+          : "=&v"(th[0]), "=&v"(th[1]), "=&v"(th[2]), "=&v"(th[3]),
+            "=&v"(th[4]), "=&v"(th[5]), "=&v"(th[6]), "=&v"(th[7])
+          : "v"(ta));
+    }
+    if (k < 0) {
+      if (acc[0][0][0] > 1e29f) cand_scores[0] = acc[0][0][0];
+      continue;
+    }
+    // any-hit test: fmax drops a NaN score exactly as v > theta does
+    bool hit = false;
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float mx = __builtin_fmaxf(
+            __builtin_fmaxf(acc[m][0][r], acc[m][1][r]),
+            __builtin_fmaxf(acc[m][2][r], acc[m][3][r]));
+        hit |= mx > th[m][r];
+      }
+    if (__builtin_amdgcn_ballot_w64(hit) == 0) continue;
+    // slow path. lq is laundered per tile so the 32 per-row candidate
+    // pointers (grow * cap, 64-bit) are formed here, on the rare hit,
+    // not hoisted into block-lifetime registers and scratch
+    int lq = lane >> 4;
+    asm volatile("" : "+v"(lq));
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float v = acc[m][n][r];
+          if (!(v > th[m][r])) continue;
+          int row = wm * 128 + m * 16 + lq * 4 + r;
+          long long grow = row0 + row;
+          if (grow >= nq) continue;
+          long long col = x0 + wn * 64 + n * 16 + (lane & 15);
+          if (col >= x_end) continue;
+          int pos = atomicAdd(&tc_n[grow], 1);
+          if (pos < cap) {
+            cand_scores[grow * cap + pos] = v;
+            cand_ids[grow * cap + pos] = int32_t(col);
+          }
+        }
+  }
+}
+
+// ===========================================================================
 // fp4x4 threshold scan v5: v3's 2-pair intervals + tile-resident scales.
 // Q block-scales are invariant across x tiles — staged transposed
 // (SCALE_PITCH sheets) once per BLOCK, read as 8 conflict-free b64 per

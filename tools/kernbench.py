@@ -108,9 +108,40 @@ def threshold_bench():
         print(f"{name:24s} {ms:9.2f} ms   {2*nq*rows*dim/1e12/ms*1000:7.1f} TF/s")
 
 
+def fp4_scan_bench(variants=(("v3", 2), ("v7", 7)), iters=5):
+    """fp4x4 threshold scan at 4.2M x 4096 x 1024 with production-like
+    theta (tools/ab_fp4v2.py): full vs scan-only (epilogue skipped) per
+    kernel variant; the difference is that kernel's epilogue share."""
+    import torch
+    from vainplex_openclaw_amd.ops import gpu as g
+    torch.manual_seed(7)
+    dev = "cuda:0"
+    rows, nq, dim, cap = 4_194_304, 4096, 1024, 1024
+    X = torch.nn.functional.normalize(torch.randn(rows, dim, device=dev), dim=1).bfloat16()
+    Q = torch.nn.functional.normalize(torch.randn(nq, dim, device=dev), dim=1).bfloat16()
+    X4, XS = g.to_fp4_mx(X)
+    Q4, QS = g.to_fp4_mx(Q)
+    s = torch.matmul(Q, X[:65536].T).float()
+    theta = (s.mean(dim=1) + 4.2 * s.std(dim=1)).contiguous()
+    del X, s
+    for name, variant in variants:
+        ms = {}
+        for mode, scan_only in (("full", False), ("scan-only", True)):
+            fn = lambda: g.ext().topk_scan_threshold_fp4x4(
+                Q4, QS, X4, XS, theta, cap, 0, variant, scan_only)
+            ms[mode] = timed(fn, iters=iters, warmup=2)
+            hits = int(fn()[2].sum())
+            print(f"fp4x4 {name} {mode:10s} {ms[mode]:9.3f} ms   "
+                  f"{2*nq*rows*dim/1e12/ms[mode]*1000:7.1f} TF/s   hits {hits}")
+        print(f"fp4x4 {name} epilogue   {ms['full'] - ms['scan-only']:9.3f} ms   "
+              f"{100 * (ms['full'] - ms['scan-only']) / ms['full']:5.1f} % of full")
+
+
 if __name__ == "__main__":
     import sys as _sys
-    if "--scan-only" in _sys.argv:
+    if "--fp4-scan" in _sys.argv:
+        fp4_scan_bench()
+    elif "--scan-only" in _sys.argv:
         scan_only_bench()
     elif "--threshold" in _sys.argv:
         threshold_bench()
