@@ -26,7 +26,8 @@ __global__ void encode_messages_kernel(const uint8_t*, const int32_t*, const __b
 __global__ void gemm_nt_bf16_kernel(const __bf16*, const __bf16*, float*, __bf16*,
                                     const float*, int, int, int, int, int);
 __global__ void topk_recall_kernel(const __bf16*, const __bf16*, int, int, int, int,
-                                   int, float*, int32_t*, const float*, int32_t*, int);
+                                   int, float*, int32_t*, const float*, int32_t*, int,
+                                   const int32_t*, const int32_t*);
 __global__ void topk_recall_fp8_kernel(const uint8_t*, const uint8_t*, int, int, int,
                                        int, int, float*, int32_t*, const float*,
                                        int32_t*, int);
@@ -51,7 +52,10 @@ __global__ void topk_scan_fp4_v5_kernel(const uint8_t*, const uint8_t*, const ui
 __global__ void topk_scan_fp4_v7_kernel(const uint8_t*, const uint8_t*, const uint8_t*,
                                         const uint8_t*, int, int, int, int, int,
                                         float*, int32_t*, const float*, int32_t*, int);
-
+__global__ void topk_scan_fp4_owned_kernel(const uint8_t*, const uint8_t*, const uint8_t*,
+                                           const uint8_t*, int, int, int, int, int,
+                                           float*, int32_t*, const float*, int32_t*, int,
+                                           const int32_t*, const int32_t*);
 
 __global__ void topk_merge_kernel(const float*, const int32_t*, int, int, int,
                                   float*, int32_t*);
@@ -200,7 +204,10 @@ torch::Tensor encode_messages(torch::Tensor bytes, torch::Tensor offsets,
   int vocab = embed.size(0);
   int dim = embed.size(1);
   TORCH_CHECK((vocab & (vocab - 1)) == 0, "vocab must be a power of two");
-  TORCH_CHECK(dim % 1024 == 0, "dim must be a multiple of 1024");
+  // the kernel walks 1024-dim chunks (256 threads x 4 dims) and guards the
+  // tail of a single short chunk
+  TORCH_CHECK(dim % 1024 == 0 || (dim < 1024 && dim % 4 == 0),
+              "dim must be a multiple of 1024, or a multiple of 4 below 1024");
   int n = offsets.numel() - 1;
   auto out = torch::empty({n, dim}, embed.options());
   hipLaunchKernelGGL(encode_messages_kernel, dim3(n), dim3(256), 0, cur_stream(),
@@ -235,12 +242,38 @@ torch::Tensor gemm_nt(torch::Tensor A, torch::Tensor B,
   return C;
 }
 
+// Owner filter operands: xowner int32 [nx] (values >= 0), qowner int32
+// [nq] (< 0 = unfiltered). Both or neither.
+static void check_owners(const torch::Tensor& xowner, const torch::Tensor& qowner,
+                         long long nx, long long nq) {
+  CHECK_GPU(xowner); CHECK_CONTIG(xowner); CHECK_GPU(qowner); CHECK_CONTIG(qowner);
+  TORCH_CHECK(xowner.dtype() == torch::kInt32 && qowner.dtype() == torch::kInt32,
+              "xowner and qowner must be int32");
+  TORCH_CHECK(xowner.dim() == 1 && xowner.numel() == nx,
+              "xowner must have one entry per index row");
+  TORCH_CHECK(qowner.dim() == 1 && qowner.numel() == nq,
+              "qowner must have one entry per query");
+}
+
+static bool have_owners(const c10::optional<torch::Tensor>& xowner,
+                        const c10::optional<torch::Tensor>& qowner,
+                        long long nx, long long nq) {
+  TORCH_CHECK(xowner.has_value() == qowner.has_value(),
+              "xowner and qowner must be given together");
+  if (!xowner.has_value()) return false;
+  check_owners(*xowner, *qowner, nx, nq);
+  return true;
+}
+
 std::vector<torch::Tensor> topk_recall(torch::Tensor Q, torch::Tensor X, int64_t k,
-                                       int64_t n_swaths) {
+                                       int64_t n_swaths,
+                                       c10::optional<torch::Tensor> xowner,
+                                       c10::optional<torch::Tensor> qowner) {
   CHECK_GPU(Q); CHECK_CONTIG(Q); CHECK_GPU(X); CHECK_CONTIG(X);
   TORCH_CHECK(Q.dtype() == torch::kBFloat16 && X.dtype() == torch::kBFloat16);
   int nq = Q.size(0), D = Q.size(1);
   long long nx = X.size(0);
+  bool owned = have_owners(xowner, qowner, nx, nq);
   TORCH_CHECK(X.size(1) == D && D % 64 == 0, "D must be a multiple of 64");
   TORCH_CHECK(k >= 1 && k <= 32, "k in [1,32]");
   int n_qblocks = (nq + 255) / 256;  // BM=256 (topk_recall.hip v3)
@@ -263,7 +296,9 @@ std::vector<torch::Tensor> topk_recall(torch::Tensor Q, torch::Tensor X, int64_t
                      reinterpret_cast<const __bf16*>(Q.data_ptr()),
                      reinterpret_cast<const __bf16*>(X.data_ptr()), nq, (int)nx, D,
                      (int)k, (int)n_swaths, cand_s.data_ptr<float>(),
-                     cand_i.data_ptr<int32_t>(), nullptr, nullptr, 0);
+                     cand_i.data_ptr<int32_t>(), nullptr, nullptr, 0,
+                     owned ? xowner->data_ptr<int32_t>() : nullptr,
+                     owned ? qowner->data_ptr<int32_t>() : nullptr);
   auto out_s = torch::empty({nq, k}, f32opts);
   auto out_i = torch::empty({nq, k}, i32opts);
   int waves_per_block = 4;
@@ -372,10 +407,13 @@ torch::Tensor audit_pack(torch::Tensor verdict, torch::Tensor risk, torch::Tenso
 }
 
 
-std::vector<torch::Tensor> topk_scan_threshold_fp4x4(
+// Shared body of the unfiltered and the owner-filtered fp4x4 bindings:
+// same operand checks, swath heuristic and candidate buffers. With owners
+// the launch is topk_scan_fp4_owned_kernel and variant_arg is unused.
+static std::vector<torch::Tensor> fp4x4_scan(
     torch::Tensor Q4, torch::Tensor QS, torch::Tensor X4, torch::Tensor XS,
     torch::Tensor theta, int64_t cap, int64_t n_swaths, int64_t variant_arg,
-    bool scan_only) {
+    bool scan_only, const torch::Tensor* xowner, const torch::Tensor* qowner) {
   // both operands MXFP4 (csrc topk_scan_fp4_kernel); scores at x1.
   // variant_arg: -1 = environment/default, 0 = v1, 1 = v2, 2 = v3,
   // 4 = v5, 7 = v7. scan_only runs the K-loops without the epilogue
@@ -389,6 +427,7 @@ std::vector<torch::Tensor> topk_scan_threshold_fp4x4(
   TORCH_CHECK(QS.size(0) == nq && QS.size(1) == D / 32);
   TORCH_CHECK(X4.size(1) == D / 2 && XS.size(0) == nx && XS.size(1) == D / 32);
   TORCH_CHECK(theta.numel() == nq && cap >= 32 && cap <= 4096);
+  if (xowner != nullptr) check_owners(*xowner, *qowner, nx, nq);
   // v7 (v3 + wave any-hit fast path, hoisted staging addresses, Q scale
   // sheet staged once) is the default: bit-exact vs v1 and measured 11.0
   // vs 15.4 ms at 4.2M x 4096. Env overrides for A/B.
@@ -416,6 +455,17 @@ std::vector<torch::Tensor> topk_scan_threshold_fp4x4(
   auto cand_i = torch::full({(long long)nq, cap}, -1, i32opts);
   auto counts = torch::zeros({(long long)nq}, i32opts);
   dim3 grid((unsigned)(n_qblocks * n_swaths));
+  if (xowner != nullptr) {
+    hipLaunchKernelGGL(topk_scan_fp4_owned_kernel, grid, dim3(512), 0, cur_stream(),
+                       Q4.data_ptr<uint8_t>(), QS.data_ptr<uint8_t>(),
+                       X4.data_ptr<uint8_t>(), XS.data_ptr<uint8_t>(),
+                       nq, (int)nx, D, 1, (int)n_swaths,
+                       cand_s.data_ptr<float>(), cand_i.data_ptr<int32_t>(),
+                       theta.data_ptr<float>(), counts.data_ptr<int32_t>(),
+                       (int)cap, xowner->data_ptr<int32_t>(),
+                       qowner->data_ptr<int32_t>());
+    return {cand_s, cand_i, counts};
+  }
   auto kern = variant == 7 ? topk_scan_fp4_v7_kernel
             : variant == 4 ? topk_scan_fp4_v5_kernel
             : variant == 2 ? topk_scan_fp4_v3_kernel
@@ -430,9 +480,30 @@ std::vector<torch::Tensor> topk_scan_threshold_fp4x4(
   return {cand_s, cand_i, counts};
 }
 
+std::vector<torch::Tensor> topk_scan_threshold_fp4x4(
+    torch::Tensor Q4, torch::Tensor QS, torch::Tensor X4, torch::Tensor XS,
+    torch::Tensor theta, int64_t cap, int64_t n_swaths, int64_t variant_arg,
+    bool scan_only) {
+  return fp4x4_scan(Q4, QS, X4, XS, theta, cap, n_swaths, variant_arg, scan_only,
+                    nullptr, nullptr);
+}
+
+// Owner-filtered fp4x4 threshold scan (csrc topk_scan_fp4_owned_kernel):
+// appends only (query, row) pairs with qowner[query] < 0 or xowner[row] ==
+// qowner[query].
+std::vector<torch::Tensor> topk_scan_threshold_fp4x4_owned(
+    torch::Tensor Q4, torch::Tensor QS, torch::Tensor X4, torch::Tensor XS,
+    torch::Tensor theta, torch::Tensor xowner, torch::Tensor qowner, int64_t cap,
+    int64_t n_swaths) {
+  return fp4x4_scan(Q4, QS, X4, XS, theta, cap, n_swaths, -1, false, &xowner,
+                    &qowner);
+}
+
 std::vector<torch::Tensor> topk_scan_threshold(torch::Tensor Q, torch::Tensor X,
                                                torch::Tensor theta, int64_t cap,
-                                               int64_t n_swaths, bool fp8, bool mx) {
+                                               int64_t n_swaths, bool fp8, bool mx,
+                                               c10::optional<torch::Tensor> xowner,
+                                               c10::optional<torch::Tensor> qowner) {
   // threshold-scan mode: append every score > theta[q] to a per-query
   // candidate buffer (no top-k maintenance in-kernel)
   CHECK_GPU(Q); CHECK_CONTIG(Q); CHECK_GPU(X); CHECK_CONTIG(X);
@@ -443,6 +514,9 @@ std::vector<torch::Tensor> topk_scan_threshold(torch::Tensor Q, torch::Tensor X,
   TORCH_CHECK(theta.numel() == nq);
   TORCH_CHECK(X.size(1) == D && D % 64 == 0);
   TORCH_CHECK(cap >= 32 && cap <= 4096);
+  bool owned = have_owners(xowner, qowner, nx, nq);
+  TORCH_CHECK(!owned || !(fp8 || mx),
+              "owner filter: bf16 and fp4x4 scans only");
   static const int variant = [] {
     const char* e = getenv("VAINPLEX_FP4_V2");
     return (e != nullptr && e[0] == '1') ? 1 : 0;  // pipelined v2 opt-in
@@ -483,7 +557,9 @@ std::vector<torch::Tensor> topk_scan_threshold(torch::Tensor Q, torch::Tensor X,
                        reinterpret_cast<const __bf16*>(X.data_ptr()), nq, (int)nx,
                        D, 1, (int)n_swaths, cand_s.data_ptr<float>(),
                        cand_i.data_ptr<int32_t>(), theta.data_ptr<float>(),
-                       counts.data_ptr<int32_t>(), (int)cap);
+                       counts.data_ptr<int32_t>(), (int)cap,
+                       owned ? xowner->data_ptr<int32_t>() : nullptr,
+                       owned ? qowner->data_ptr<int32_t>() : nullptr);
   }
   return {cand_s, cand_i, counts};
 }
@@ -501,7 +577,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_nt", &gemm_nt, "bf16 NT GEMM with fused epilogue",
         py::arg("A"), py::arg("B"), py::arg("bias") = c10::nullopt,
         py::arg("act") = 0, py::arg("out_bf16") = false);
-  m.def("topk_recall", &topk_recall, "Fused cosine top-k recall");
+  m.def("topk_recall", &topk_recall, "Fused cosine top-k recall",
+        py::arg("Q"), py::arg("X"), py::arg("k"), py::arg("n_swaths"),
+        py::arg("xowner") = c10::nullopt, py::arg("qowner") = c10::nullopt);
   m.def("topk_scan_only", [](torch::Tensor Q, torch::Tensor X, int64_t n_swaths, bool fp8,
                              bool mx) {
     // perf diagnosis: run the scan loop with the top-k phase skipped
@@ -529,7 +607,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                          reinterpret_cast<const __bf16*>(Q.data_ptr()),
                          reinterpret_cast<const __bf16*>(X.data_ptr()), nq, (int)nx,
                          D, -1, (int)n_swaths, cand_s.data_ptr<float>(),
-                         cand_i.data_ptr<int32_t>(), nullptr, nullptr, 0);
+                         cand_i.data_ptr<int32_t>(), nullptr, nullptr, 0,
+                         nullptr, nullptr);
     }
   }, "scan-only diagnosis", py::arg("Q"), py::arg("X"), py::arg("n_swaths"),
      py::arg("fp8") = false, py::arg("mx") = false);
@@ -537,7 +616,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topk_scan_threshold", &topk_scan_threshold,
         "threshold-scan candidate collection (bf16, fp8 or MX-fp8)",
         py::arg("Q"), py::arg("X"), py::arg("theta"), py::arg("cap"),
-        py::arg("n_swaths"), py::arg("fp8") = false, py::arg("mx") = false);
+        py::arg("n_swaths"), py::arg("fp8") = false, py::arg("mx") = false,
+        py::arg("xowner") = c10::nullopt, py::arg("qowner") = c10::nullopt);
   m.def("topk_scan_threshold_fp4",
         [](torch::Tensor Q8, torch::Tensor X4, torch::Tensor XS,
            torch::Tensor theta, int64_t cap, int64_t n_swaths) {
@@ -580,6 +660,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Q4"), py::arg("QS"), py::arg("X4"), py::arg("XS"),
         py::arg("theta"), py::arg("cap"), py::arg("n_swaths"),
         py::arg("variant") = -1, py::arg("scan_only") = false);
+  m.def("topk_scan_threshold_fp4x4_owned", &topk_scan_threshold_fp4x4_owned,
+        "owner-filtered full-MXFP4 threshold scan (agent-isolated recall)",
+        py::arg("Q4"), py::arg("QS"), py::arg("X4"), py::arg("XS"),
+        py::arg("theta"), py::arg("xowner"), py::arg("qowner"), py::arg("cap"),
+        py::arg("n_swaths"));
   m.def("edit_distance", [](torch::Tensor bytes, torch::Tensor offsets) {
     // batched Levenshtein over string PAIRS: offsets has 2*n+1 entries;
     // pair i = strings (2i, 2i+1) in the packed byte buffer

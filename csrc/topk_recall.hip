@@ -84,7 +84,13 @@ topk_recall_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ X,
                    // no queue, no drain, no per-tile barriers. cand_scores/
                    // cand_ids are then [nq][cap]; tc_n[nq] counts appends.
                    const float* __restrict__ theta,
-                   int32_t* __restrict__ tc_n, int cap) {
+                   int32_t* __restrict__ tc_n, int cap,
+                   // owner filter (both nullptr = off): a (query, row) pair
+                   // is eligible iff qowner[query] < 0 or xowner[row] ==
+                   // qowner[query]; ineligible scores are dropped before
+                   // the append / push
+                   const int32_t* __restrict__ xowner,
+                   const int32_t* __restrict__ qowner) {
   // Triple-buffered Q+X K-tiles: staging runs TWO K-steps ahead of
   // compute, synchronized with counted s_waitcnt vmcnt(4) + raw
   // s_barrier. (__syncthreads() makes the compiler drain the whole
@@ -111,6 +117,7 @@ topk_recall_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ X,
   // rare; the scan's fixed cost measured ~half of kernel time)
   __shared__ float block_tmin[2];
   __shared__ int tmin_dirty;
+  __shared__ int32_t row_owner[BM];  // owner filter: -1 = sees every row
 
   int S = n_swaths;
   int qb = blockIdx.x / S;      // same-swath groups land on one XCD
@@ -126,6 +133,7 @@ topk_recall_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ X,
     // threshold mode reuses row_min as the per-row fixed threshold
     row_min[i] = (theta != nullptr && row0 + i < nq) ? theta[row0 + i] : -1e30f;
     row_min_slot[i] = 0;
+    row_owner[i] = (qowner != nullptr && row0 + i < nq) ? qowner[row0 + i] : -1;
   }
   for (int i = threadIdx.x; i < BM * TOPK_MAX; i += blockDim.x)
     topk_vals[i / TOPK_MAX][i % TOPK_MAX] = -1e30f;
@@ -241,6 +249,10 @@ topk_recall_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ X,
             if (grow >= nq) continue;
             long long col = x0 + wn * 64 + n * 16 + (lane & 15);
             if (col >= x_end) continue;
+            if (xowner != nullptr) {
+              int32_t qo = row_owner[row];
+              if (qo >= 0 && xowner[col] != qo) continue;
+            }
             int pos = atomicAdd(&tc_n[grow], 1);
             if (pos < cap) {
               cand_scores[grow * cap + pos] = v;
@@ -287,6 +299,10 @@ topk_recall_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ X,
             if (col >= x_end) continue;
             float v = acc[m][n][r];
             if (!(v > row_min[row])) continue;
+            if (xowner != nullptr) {
+              int32_t qo = row_owner[row];
+              if (qo >= 0 && xowner[col] != qo) continue;
+            }
             int idx = atomicAdd(&q_count, 1);
             if (idx < QCAP) {
               q_score[idx] = v;
@@ -2109,3 +2125,281 @@ topk_scan_fp4_v5_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
 }
 
 
+
+// ===========================================================================
+// fp4x4 threshold scan, owner-filtered (agent-isolated recall): v7's tile
+// geometry, LDS image, K-loop, staging and candidate-append format with an
+// owner-aware epilogue. A (query, row) pair is eligible iff the query is
+// unfiltered (qowner < 0) or xowner[row] == qowner[query].
+//  - query owners: staged once per block into LDS (1 KB), -1 = unfiltered,
+//    -2 = garbage row (grow >= nq, matches nothing). Read like the
+//    thresholds, 8 ds_read_b128 per lane, only after the score gate passes.
+//  - row owners: four per-lane global loads at the tile head (the lane's
+//    columns n*16 + (lane&15)), landed by the first interval's vmcnt(0);
+//    columns past x_end carry -3 (matches nothing, not even an unfiltered
+//    query).
+//  - gates: v7's score-only any-hit ballot first. Per-owner thresholds sit
+//    lower than a whole-index threshold, so with many owners that gate
+//    passes in most wave-tiles; a second ballot over (score > theta &&
+//    owner match) keeps the 128-element compare/append loop for the
+//    wave-tiles that really append. A wave whose 128 query rows include an
+//    unfiltered query skips the second gate (block-lifetime flag): the
+//    equality test cannot express "matches every row" and the loop is
+//    exact either way.
+// ===========================================================================
+
+typedef int32_t i32x4_own __attribute__((ext_vector_type(4)));
+
+extern "C" __global__ void __launch_bounds__(TK_THREADS)
+topk_scan_fp4_owned_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restrict__ QS,
+                           const uint8_t* __restrict__ X4, const uint8_t* __restrict__ XS,
+                           int nq, int nx, int D, int k, int n_swaths,
+                           float* __restrict__ cand_scores,
+                           int32_t* __restrict__ cand_ids,
+                           const float* __restrict__ theta,
+                           int32_t* __restrict__ tc_n, int cap,
+                           const int32_t* __restrict__ xowner,
+                           const int32_t* __restrict__ qowner) {
+  __shared__ bf16 lds_q[4 * BM * BK];
+  __shared__ bf16 lds_x[4 * BN * BK];
+  __shared__ uint8_t lds_qs[BM * 32];
+  __shared__ uint8_t lds_xs2[BN * 32];
+  __shared__ __attribute__((aligned(16))) float row_min[BM];
+  __shared__ __attribute__((aligned(16))) int32_t row_owner[BM];
+#define QP4O(buf) (lds_q + (buf) * BM * BK)
+#define XP4O(buf) (lds_x + (buf) * BN * BK)
+
+  int S = n_swaths;
+  int qb = blockIdx.x / S;
+  int swath = blockIdx.x % S;
+  long long row0 = (long long)qb * BM;
+
+  long long per = ((long long)nx + S - 1) / S;
+  per = ((per + BN - 1) / BN) * BN;
+  long long x_begin = (long long)swath * per;
+  long long x_end = min((long long)nx, x_begin + per);
+  if (x_begin >= x_end) return;
+
+  for (int i = threadIdx.x; i < BM; i += blockDim.x) {
+    bool live = row0 + i < nq;
+    row_min[i] = (theta != nullptr && live) ? theta[row0 + i] : -1e30f;
+    int32_t qo = live ? qowner[row0 + i] : -2;
+    row_owner[i] = (live && qo < 0) ? -1 : qo;
+  }
+  __syncthreads();
+
+  int wid = wave_id();
+  uint32_t wu = (uint32_t)__builtin_amdgcn_readfirstlane(wid);
+  int wm = wid >> 2, wn = wid & 3;
+  int lane = lane_id();
+  int lrow = lane & 15;
+  int kgrp = lane >> 4;
+  int np = D / (2 * BK_F8);
+  int sb = D / 32;
+  uint32_t ldb = (uint32_t)(D / 2);  // row pitch in bytes
+
+  // does any of this wave's 128 query rows see every row?
+  bool wave_wild = __builtin_amdgcn_ballot_w64(
+      row_owner[wm * 128 + lane] == -1 || row_owner[wm * 128 + 64 + lane] == -1) != 0;
+
+  uint32_t qoff[2], xoff[2];
+  const uint8_t* qbase = Q4 + row0 * (long long)ldb;
+  stage_row_offsets(wu, (uint32_t)lane, (uint32_t)min((long long)BM, nq - row0),
+                    ldb, qoff);
+
+  auto stage_pair = [&](long long xt, int s) {
+    stage_tile_off(qbase + s * 64, qoff, QP4O(s & 3), wu);
+    stage_tile_off(X4 + xt * (long long)ldb + s * 64, xoff, XP4O(s & 3), wu);
+  };
+  auto stage_head = [&](long long xt) {
+    stage_row_offsets(wu, (uint32_t)lane, (uint32_t)min((long long)BN, nx - xt),
+                      ldb, xoff);
+    stage_scale_rows(XS, sb, xt, (long long)nx, lds_xs2, BN);
+    stage_pair(xt, 0);
+    if (np > 1) stage_pair(xt, 1);
+  };
+
+  stage_scale_rows(QS, sb, row0, (long long)nq, lds_qs, BM);
+
+  for (long long x0 = x_begin; x0 < x_end; x0 += BN) {
+    f32x4 acc[8][4] = {};
+    // the lane's 4 row owners; they fly under the K-loop
+    int32_t xo[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      long long col = x0 + wn * 64 + n * 16 + lrow;
+      xo[n] = col < x_end ? xowner[col] : -3;
+    }
+    stage_head(x0);
+    for (int p = 0; p < np; p += 2) {
+      int pe = min(p + 2, np);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      if (p + 2 < np) stage_pair(x0, p + 2);
+      if (p + 3 < np) stage_pair(x0, p + 3);
+      for (int pc = p; pc < pe; ++pc) {
+        uint32_t xrow_base = (uint32_t)(wn * 64 + lrow);
+        uint32_t qrow_base = (uint32_t)(wm * 128 + lrow);
+        uint32_t xaddr = (uint32_t)(size_t)XP4O(pc & 3)
+                         + lds_off_bytes(xrow_base, (uint32_t)kgrp);
+        uint32_t qaddr = (uint32_t)(size_t)QP4O(pc & 3)
+                         + lds_off_bytes(qrow_base, (uint32_t)kgrp);
+        uint32_t sst = 16u * (uint32_t)sb;
+        uint32_t xs_a = (uint32_t)(size_t)lds_xs2 + xrow_base * (uint32_t)sb
+                        + (uint32_t)(pc * 4 + kgrp);
+        uint32_t qs_a = (uint32_t)(size_t)lds_qs + qrow_base * (uint32_t)sb
+                        + (uint32_t)(pc * 4 + kgrp);
+        bf16x8 xf[4], qf[8];
+        uint32_t xs_v[4], qs_v[8];
+        asm volatile(
+            "ds_read_b128 %0, %8\n\t"
+            "ds_read_b128 %1, %8 offset:1024\n\t"
+            "ds_read_b128 %2, %8 offset:2048\n\t"
+            "ds_read_b128 %3, %8 offset:3072\n\t"
+            "ds_read_u8 %4, %9\n\t"
+            "ds_read_u8 %5, %10\n\t"
+            "ds_read_u8 %6, %11\n\t"
+            "ds_read_u8 %7, %12\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(xf[0]), "=&v"(xf[1]), "=&v"(xf[2]), "=&v"(xf[3]),
+              "=&v"(xs_v[0]), "=&v"(xs_v[1]), "=&v"(xs_v[2]), "=&v"(xs_v[3])
+            : "v"(xaddr), "v"(xs_a), "v"(xs_a + sst), "v"(xs_a + 2 * sst),
+              "v"(xs_a + 3 * sst));
+        asm volatile(
+            "ds_read_b128 %0, %16\n\t"
+            "ds_read_b128 %1, %16 offset:1024\n\t"
+            "ds_read_b128 %2, %16 offset:2048\n\t"
+            "ds_read_b128 %3, %16 offset:3072\n\t"
+            "ds_read_b128 %4, %16 offset:4096\n\t"
+            "ds_read_b128 %5, %16 offset:5120\n\t"
+            "ds_read_b128 %6, %16 offset:6144\n\t"
+            "ds_read_b128 %7, %16 offset:7168\n\t"
+            "ds_read_u8 %8, %17\n\t"
+            "ds_read_u8 %9, %18\n\t"
+            "ds_read_u8 %10, %19\n\t"
+            "ds_read_u8 %11, %20\n\t"
+            "ds_read_u8 %12, %21\n\t"
+            "ds_read_u8 %13, %22\n\t"
+            "ds_read_u8 %14, %23\n\t"
+            "ds_read_u8 %15, %24\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(qf[0]), "=&v"(qf[1]), "=&v"(qf[2]), "=&v"(qf[3]),
+              "=&v"(qf[4]), "=&v"(qf[5]), "=&v"(qf[6]), "=&v"(qf[7]),
+              "=&v"(qs_v[0]), "=&v"(qs_v[1]), "=&v"(qs_v[2]), "=&v"(qs_v[3]),
+              "=&v"(qs_v[4]), "=&v"(qs_v[5]), "=&v"(qs_v[6]), "=&v"(qs_v[7])
+            : "v"(qaddr), "v"(qs_a), "v"(qs_a + sst), "v"(qs_a + 2 * sst),
+              "v"(qs_a + 3 * sst), "v"(qs_a + 4 * sst), "v"(qs_a + 5 * sst),
+              "v"(qs_a + 6 * sst), "v"(qs_a + 7 * sst));
+        v8i_mx xv[4], qv[8];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) xv[n] = fp4_frag(xf[n]);
+#pragma unroll
+        for (int m = 0; m < 8; ++m) qv[m] = fp4_frag(qf[m]);
+#pragma unroll
+        for (int m = 0; m < 8; ++m)
+#pragma unroll
+          for (int n = 0; n < 4; ++n)
+            acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+                qv[m], xv[n], acc[m][n], 4 /*A fp4*/, 4 /*B fp4*/,
+                0, (int)qs_v[m], 0, (int)xs_v[n]);
+      }
+    }
+    // as in v7: nothing in flight; the barrier orders every wave's last
+    // fragment reads before the next tile's head restages buffers 0,1
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    f32x4 th[8];
+    {
+      uint32_t ta = (uint32_t)(size_t)row_min
+                    + (uint32_t)(wm * 128 + (lane >> 4) * 4) * 4u;
+      asm volatile(
+          "ds_read_b128 %0, %8\n\t"
+          "ds_read_b128 %1, %8 offset:64\n\t"
+          "ds_read_b128 %2, %8 offset:128\n\t"
+          "ds_read_b128 %3, %8 offset:192\n\t"
+          "ds_read_b128 %4, %8 offset:256\n\t"
+          "ds_read_b128 %5, %8 offset:320\n\t"
+          "ds_read_b128 %6, %8 offset:384\n\t"
+          "ds_read_b128 %7, %8 offset:448\n\t"
+          "s_waitcnt lgkmcnt(0)"
+          : "=&v"(th[0]), "=&v"(th[1]), "=&v"(th[2]), "=&v"(th[3]),
+            "=&v"(th[4]), "=&v"(th[5]), "=&v"(th[6]), "=&v"(th[7])
+          : "v"(ta));
+    }
+    if (k < 0) {
+      if (acc[0][0][0] > 1e29f) cand_scores[0] = acc[0][0][0];
+      continue;
+    }
+    // gate 1 (v7's): score-only any-hit
+    bool hit = false;
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float mx = __builtin_fmaxf(
+            __builtin_fmaxf(acc[m][0][r], acc[m][1][r]),
+            __builtin_fmaxf(acc[m][2][r], acc[m][3][r]));
+        hit |= mx > th[m][r];
+      }
+    if (__builtin_amdgcn_ballot_w64(hit) == 0) continue;
+    // the lane's 32 query owners, qo[m][r] laid out like th[m][r]
+    i32x4_own qo[8];
+    {
+      uint32_t oa = (uint32_t)(size_t)row_owner
+                    + (uint32_t)(wm * 128 + (lane >> 4) * 4) * 4u;
+      asm volatile(
+          "ds_read_b128 %0, %8\n\t"
+          "ds_read_b128 %1, %8 offset:64\n\t"
+          "ds_read_b128 %2, %8 offset:128\n\t"
+          "ds_read_b128 %3, %8 offset:192\n\t"
+          "ds_read_b128 %4, %8 offset:256\n\t"
+          "ds_read_b128 %5, %8 offset:320\n\t"
+          "ds_read_b128 %6, %8 offset:384\n\t"
+          "ds_read_b128 %7, %8 offset:448\n\t"
+          "s_waitcnt lgkmcnt(0)"
+          : "=&v"(qo[0]), "=&v"(qo[1]), "=&v"(qo[2]), "=&v"(qo[3]),
+            "=&v"(qo[4]), "=&v"(qo[5]), "=&v"(qo[6]), "=&v"(qo[7])
+          : "v"(oa));
+    }
+    // gate 2: any (score > theta && owner match) in the wave. Scores of
+    // foreign columns are replaced by -inf, then the test is gate 1's.
+    if (!wave_wild) {
+      bool hit2 = false;
+#pragma unroll
+      for (int m = 0; m < 8; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float mx = -__builtin_inff();
+#pragma unroll
+          for (int n = 0; n < 4; ++n)
+            mx = __builtin_fmaxf(mx, qo[m][r] == xo[n] ? acc[m][n][r]
+                                                      : -__builtin_inff());
+          hit2 |= mx > th[m][r];
+        }
+      if (__builtin_amdgcn_ballot_w64(hit2) == 0) continue;
+    }
+    int lq = lane >> 4;
+    asm volatile("" : "+v"(lq));
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float v = acc[m][n][r];
+          bool eligible = qo[m][r] == xo[n] || qo[m][r] == -1;
+          if (!(v > th[m][r] && eligible)) continue;
+          int row = wm * 128 + m * 16 + lq * 4 + r;
+          long long grow = row0 + row;
+          if (grow >= nq) continue;
+          long long col = x0 + wn * 64 + n * 16 + (lane & 15);
+          if (col >= x_end) continue;
+          int pos = atomicAdd(&tc_n[grow], 1);
+          if (pos < cap) {
+            cand_scores[grow * cap + pos] = v;
+            cand_ids[grow * cap + pos] = int32_t(col);
+          }
+        }
+  }
+}

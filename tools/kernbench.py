@@ -137,9 +137,75 @@ def fp4_scan_bench(variants=(("v3", 2), ("v7", 7)), iters=5):
               f"{100 * (ms['full'] - ms['scan-only']) / ms['full']:5.1f} % of full")
 
 
+def timed_median(fn, iters=9, warmup=3):
+    """Median of per-iteration device times (ms)."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(iters):
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return sorted(ts)[len(ts) // 2]
+
+
+def fp4_owned_scan_bench(n_owners, iters=9):
+    """Cost of the in-kernel owner filter at the fp4_scan_bench shape, one
+    session: v7 and v3 unfiltered (the yardsticks), then the owned kernel
+    with 1 owner (same candidates as v7) and with `n_owners` uniform random
+    owners. Thresholds are per owner (ops.gpu.owned_thresholds) with the
+    candidate target that makes the 1-owner theta the unfiltered bench's
+    mu + 4.2 sigma, so every config expects the same candidates per query."""
+    import math
+    torch.manual_seed(7)
+    dev = "cuda:0"
+    rows, nq, dim, cap = 4_194_304, 4096, 1024, 1024
+    X = torch.nn.functional.normalize(torch.randn(rows, dim, device=dev), dim=1).bfloat16()
+    Q = torch.nn.functional.normalize(torch.randn(nq, dim, device=dev), dim=1).bfloat16()
+    X4, XS = g.to_fp4_mx(X)
+    Q4, QS = g.to_fp4_mx(Q)
+    s = torch.matmul(Q, X[:65536].T).float()
+    mu, sigma = s.mean(dim=1), s.std(dim=1)
+    del X, s
+    target = 0.5 * math.erfc(4.2 / math.sqrt(2.0)) * rows
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(11)
+
+    def owned(n):
+        xo = torch.randint(0, n, (rows,), generator=gen, dtype=torch.int32, device=dev)
+        qo = torch.randint(0, n, (nq,), generator=gen, dtype=torch.int32, device=dev)
+        n_owned = torch.bincount(xo.long(), minlength=n)[qo.long()]
+        th = g.owned_thresholds(mu, sigma, n_owned, target).contiguous()
+        return lambda: g.ext().topk_scan_threshold_fp4x4_owned(
+            Q4, QS, X4, XS, th, xo, qo, cap, 0)
+
+    theta = (mu + 4.2 * sigma).contiguous()
+    configs = [
+        ("v7 unfiltered", lambda: g.ext().topk_scan_threshold_fp4x4(
+            Q4, QS, X4, XS, theta, cap, 0, 7, False)),
+        ("v3 unfiltered", lambda: g.ext().topk_scan_threshold_fp4x4(
+            Q4, QS, X4, XS, theta, cap, 0, 2, False)),
+        ("owned, 1 owner", owned(1)),
+    ]
+    if n_owners > 1:
+        configs.append((f"owned, {n_owners} owners", owned(n_owners)))
+    for name, fn in configs:
+        ms = timed_median(fn, iters=iters)
+        hits = int(fn()[2].sum())
+        print(f"fp4x4 {name:20s} {ms:9.3f} ms (median of {iters})   "
+              f"{2*nq*rows*dim/1e12/ms*1000:7.1f} TF/s   hits {hits}")
+
+
 if __name__ == "__main__":
     import sys as _sys
-    if "--fp4-scan" in _sys.argv:
+    if "--fp4-scan" in _sys.argv and "--owners" in _sys.argv:
+        fp4_owned_scan_bench(int(_sys.argv[_sys.argv.index("--owners") + 1]))
+    elif "--fp4-scan" in _sys.argv:
         fp4_scan_bench()
     elif "--scan-only" in _sys.argv:
         scan_only_bench()

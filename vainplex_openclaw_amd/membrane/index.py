@@ -13,7 +13,7 @@ reference.
 
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -45,10 +45,15 @@ class SalienceIndex:
         if self.use_gpu:
             self._embed = torch.from_numpy(self._embed_np).to(device).bfloat16()
             self._mat = torch.empty(capacity, dim, dtype=torch.bfloat16, device=device)
+            self._owner = torch.empty(capacity, dtype=torch.int32, device=device)
         else:
             self._mat_np = np.zeros((capacity, dim), dtype=np.float32)
+            self._owner_np = np.zeros(capacity, dtype=np.int32)
         self.ids: List[str] = []  # row -> record id
-        self.owners: List[str] = []  # row -> agent (isolation filter)
+        self.owners: List[str] = []  # row -> agent
+        # isolation filter operands: agent -> small int, and the int32 owner
+        # vector (row -> agent int) that grows with the matrix
+        self._agent_ids: Dict[str, int] = {}
 
     @property
     def capacity(self) -> int:
@@ -65,10 +70,16 @@ class SalienceIndex:
             m = torch.empty(new_cap, self.dim, dtype=torch.bfloat16, device=self.device)
             m[: self.size] = self._mat[: self.size]
             self._mat = m
+            o = torch.empty(new_cap, dtype=torch.int32, device=self.device)
+            o[: self.size] = self._owner[: self.size]
+            self._owner = o
         else:
             m = np.zeros((new_cap, self.dim), dtype=np.float32)
             m[: self.size] = self._mat_np[: self.size]
             self._mat_np = m
+            o = np.zeros(new_cap, dtype=np.int32)
+            o[: self.size] = self._owner_np[: self.size]
+            self._owner_np = o
 
     # -- encoding ----------------------------------------------------------
     def encode(self, texts: Sequence[str]) -> "np.ndarray | torch.Tensor":
@@ -89,30 +100,38 @@ class SalienceIndex:
             return
         self._grow(self.size + n)
         feats = self.encode(texts)
+        aid = self._agent_ids.setdefault(agent, len(self._agent_ids))
         if self.use_gpu:
             self._mat[self.size : self.size + n] = feats.to(torch.bfloat16)
+            self._owner[self.size : self.size + n] = aid
         else:
             self._mat_np[self.size : self.size + n] = feats
+            self._owner_np[self.size : self.size + n] = aid
         self.ids.extend(record_ids)
         self.owners.extend([agent] * n)
         self.size += n
 
     # -- search ------------------------------------------------------------
-    def search(
-        self, agent: str, query: str, k: int, overfetch: int = 4
-    ) -> List[Tuple[str, float]]:
+    def search(self, agent: str, query: str, k: int) -> List[Tuple[str, float]]:
         """Top-k (record_id, cosine) for ONE agent. The matrix is shared
-        across agents; isolation is enforced by over-fetching and masking
-        non-owned rows (k*overfetch candidates, refill loop if needed)."""
-        if self.size == 0:
+        across agents; isolation is enforced BEFORE the top-k: the recall
+        kernel drops rows of other agents ahead of its push (CPU: their
+        similarities are masked ahead of the argsort), so an agent gets its
+        own k best rows however small its share of the index is. The GPU
+        kernel's top-k is capped at 32."""
+        aid = self._agent_ids.get(agent)
+        if self.size == 0 or aid is None or k <= 0:
             return []
         q = self.encode([query])
-        want = min(self.size, max(k * overfetch, k))
+        want = min(self.size, k)
         if self.use_gpu:
             from ..ops import gpu as g
 
             kk = min(32, want)
-            scores, ids = g.topk_recall(q.to(torch.bfloat16), self._mat[: self.size], kk)
+            qowner = torch.full((1,), aid, dtype=torch.int32, device=self.device)
+            scores, ids = g.topk_recall(
+                q.to(torch.bfloat16), self._mat[: self.size], kk,
+                owner=self._owner[: self.size], qowner=qowner)
             pairs = [
                 (int(i), float(s))
                 for s, i in zip(scores[0].tolist(), ids[0].tolist())
@@ -120,11 +139,7 @@ class SalienceIndex:
             ]
         else:
             sims = self._mat_np[: self.size] @ np.asarray(q)[0]
-            order = np.argsort(-sims)[:want]
+            own = np.flatnonzero(self._owner_np[: self.size] == aid)
+            order = own[np.argsort(-sims[own])[:want]]
             pairs = [(int(i), float(sims[i])) for i in order]
-        out = [
-            (self.ids[row], score)
-            for row, score in pairs
-            if self.owners[row] == agent
-        ]
-        return out[:k]
+        return [(self.ids[row], score) for row, score in pairs]

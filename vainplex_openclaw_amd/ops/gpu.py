@@ -9,6 +9,7 @@ tests live in `reference_*` functions.
 from __future__ import annotations
 
 import hashlib
+import math
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -167,13 +168,35 @@ def gemm_nt(
     return ext().gemm_nt(A, B, bias, act, out_bf16)
 
 
-def topk_recall(Q: torch.Tensor, X: torch.Tensor, k: int, n_swaths: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+def _owner_args(owner, qowner):
+    """Both or neither; int32 contiguous for the kernels."""
+    if (owner is None) != (qowner is None):
+        raise ValueError("owner and qowner must be given together")
+    if owner is None:
+        return None, None
+    return owner.to(torch.int32).contiguous(), qowner.to(torch.int32).contiguous()
+
+
+def topk_recall(
+    Q: torch.Tensor,
+    X: torch.Tensor,
+    k: int,
+    n_swaths: int = 0,
+    owner: Optional[torch.Tensor] = None,
+    qowner: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
     """Cosine top-k of each Q row against X (csrc/topk_recall.hip v3).
 
     Swath count: a multiple of 8 (XCD-aware grid mapping), sized so
     qblocks*swaths fills the 256 CUs, capped by the merge kernel's
     n_swaths*k <= 1024 register budget and the index size.
+
+    `owner` (int32 [nx], values >= 0) and `qowner` (int32 [nq]) turn on the
+    in-kernel isolation filter: query q sees row j only if qowner[q] < 0 or
+    owner[j] == qowner[q]. A query with fewer than k eligible rows returns
+    id -1 / score -1e30 in the unfilled slots.
     """
+    owner, qowner = _owner_args(owner, qowner)
     if n_swaths <= 0:
         qblocks = (Q.shape[0] + 255) // 256  # BM=256
         want = max(1, 256 // max(qblocks, 1))
@@ -181,8 +204,61 @@ def topk_recall(Q: torch.Tensor, X: torch.Tensor, k: int, n_swaths: int = 0) -> 
         n_swaths = min(n_swaths, (1024 // max(k, 1)) // 8 * 8)
         n_swaths = min(n_swaths, max(1, X.shape[0] // 256))
         n_swaths = max(1, n_swaths)
-    s, i = ext().topk_recall(Q, X, k, n_swaths)
+    if owner is None:
+        s, i = ext().topk_recall(Q, X, k, n_swaths)
+    else:
+        s, i = ext().topk_recall(Q, X, k, n_swaths, xowner=owner, qowner=qowner)
     return s, i
+
+
+def reference_owned_topk(
+    Q: torch.Tensor,
+    X: torch.Tensor,
+    k: int,
+    owner: torch.Tensor,
+    qowner: torch.Tensor,
+    salience: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 masked dense reference of the owner-filtered recall: mask the
+    ineligible (query, row) pairs, THEN take the top-k. Runs on any device,
+    CPU tensors included. Slots past a query's eligible rows hold id -1 /
+    score -1e30, like the kernels."""
+    scores = Q.float() @ X.float().T
+    if salience is not None:
+        scores = scores * salience.float().unsqueeze(0)
+    qo = qowner.long().unsqueeze(1)
+    eligible = (qo < 0) | (owner.long().unsqueeze(0) == qo)
+    scores = torch.where(eligible, scores, torch.full_like(scores, -1e30))
+    kk = min(k, X.shape[0])
+    top = torch.topk(scores, kk, dim=1)
+    ids = torch.where(top.values > -1e29, top.indices,
+                      torch.full_like(top.indices, -1)).to(torch.int32)
+    vals = top.values
+    if kk < k:
+        pad = (Q.shape[0], k - kk)
+        vals = torch.cat([vals, vals.new_full(pad, -1e30)], dim=1)
+        ids = torch.cat([ids, ids.new_full(pad, -1)], dim=1)
+    return vals, ids
+
+
+def owned_thresholds(
+    mu: torch.Tensor,
+    sigma: torch.Tensor,
+    n_owned: torch.Tensor,
+    target_candidates: int,
+    z_margin: float = 0.0,
+) -> torch.Tensor:
+    """Per-query scan thresholds under the owner filter. Query q competes
+    among its owner's n_owned[q] rows only, so its Gaussian tail probability
+    is p = clamp(target_candidates / n_owned, 1e-12, 0.5) and theta = mu +
+    sigma * (z(p) - z_margin) with z(p) = sqrt(2) * erfinv(1 - 2p). A query
+    whose owner has no rows gets +inf (nothing can be appended). Device
+    agnostic (CPU tensors included)."""
+    n = n_owned.to(torch.float64)
+    p = (float(target_candidates) / n.clamp_min(1.0)).clamp(1e-12, 0.5)
+    z = (math.sqrt(2.0) * torch.erfinv(1.0 - 2.0 * p) - z_margin).to(mu.dtype)
+    theta = mu + sigma * z
+    return torch.where(n_owned > 0, theta, torch.full_like(theta, float("inf")))
 
 
 def to_fp8_bytes(x: torch.Tensor, scale: float = 8.0) -> torch.Tensor:
@@ -357,6 +433,9 @@ def topk_recall_threshold(
     X4: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
     q4: bool = True,
     salience: Optional[torch.Tensor] = None,
+    owner: Optional[torch.Tensor] = None,
+    qowner: Optional[torch.Tensor] = None,
+    owner_counts: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Threshold-scan recall: per-query score thresholds estimated from a
     sampled pre-pass (Gaussian tail extrapolation), then a fixed-threshold
@@ -370,6 +449,12 @@ def topk_recall_threshold(
     rate (csrc topk_scan_mx_kernel). Queries whose candidate buffer
     underflowed (<k survivors: threshold too high for non-Gaussian score
     tails) fall back to the direct kernel.
+
+    `owner` / `qowner` (see topk_recall) filter inside the scan: thresholds
+    are set per query from the size of its owner's row set (`owner_counts`
+    = cached bincount of `owner`), every candidate is already eligible, and
+    the fallback is the owner-filtered direct kernel. Supported by the
+    fp4x4 scan (q4, D <= 1024) and the bf16 scan.
     """
     nq, D = Q.shape
     nx = X.shape[0]
@@ -377,6 +462,10 @@ def topk_recall_threshold(
     use_fp4 = X4 is not None and D % 128 == 0 and D <= 2048
     use_fp8 = X8 is not None or use_fp4
     use_mx = mx and X8 is not None and D % 128 == 0
+    owner, qowner = _owner_args(owner, qowner)
+    if owner is not None and use_fp8 and not (use_fp4 and q4 and D <= 1024):
+        raise NotImplementedError(
+            "owner-filtered recall: fp4x4 (q4, D <= 1024) and bf16 scans only")
 
     # 1. per-query score statistics from a sample (bf16 matmul)
     sample = torch.matmul(Q, X[:m].T).float()  # [nq, m]
@@ -405,14 +494,32 @@ def topk_recall_threshold(
     # widen the rescore window below (select is by NOISY scan score).
     if use_fp4:
         z = z - 0.25
-    theta = (mu + sigma * z).contiguous()
+    if owner is None:
+        theta = (mu + sigma * z).contiguous()
+    else:
+        if owner_counts is None:
+            owner_counts = torch.bincount(owner.long())
+        n_all = torch.full((1,), nx, dtype=owner_counts.dtype, device=Q.device)
+        # a query owner past the table owns no row
+        cnt = torch.cat([owner_counts.to(Q.device), n_all.new_zeros(1)])
+        qo = qowner.long()
+        n_owned = torch.where(
+            qo < 0, n_all.expand(nq),
+            cnt[qo.clamp(0, cnt.numel() - 1)])
+        theta = owned_thresholds(
+            mu, sigma, n_owned, target_candidates,
+            z_margin=0.25 if use_fp4 else 0.0).contiguous()
 
     # 2. fixed-threshold scan
     if use_fp4 and q4 and D <= 1024:
         # both operands MXFP4: scores carry no static prescale
         Q4, QS = to_fp4_mx(Q)
-        cs, ci, counts = ext().topk_scan_threshold_fp4x4(
-            Q4, QS, X4[0], X4[1], theta.contiguous(), cap, 0)
+        if owner is None:
+            cs, ci, counts = ext().topk_scan_threshold_fp4x4(
+                Q4, QS, X4[0], X4[1], theta.contiguous(), cap, 0)
+        else:
+            cs, ci, counts = ext().topk_scan_threshold_fp4x4_owned(
+                Q4, QS, X4[0], X4[1], theta, owner, qowner, cap, 0)
     elif use_fp4:
         # Q carries the only static scale (x8); X scales are per-block
         Q8 = to_fp8_bytes(Q)
@@ -423,8 +530,11 @@ def topk_recall_threshold(
         # thresholds are in fp8-score units: inputs scaled x8 each -> x64
         cs, ci, counts = ext().topk_scan_threshold(Q8, X8, (theta * 64.0).contiguous(),
                                                    cap, 0, True, use_mx)
-    else:
+    elif owner is None:
         cs, ci, counts = ext().topk_scan_threshold(Q, X, theta, cap, 0, False, False)
+    else:
+        cs, ci, counts = ext().topk_scan_threshold(
+            Q, X, theta, cap, 0, False, False, xowner=owner, qowner=qowner)
 
     # 3. mask unfilled/overflowed slots
     slot = torch.arange(cap, device=Q.device).unsqueeze(0)
@@ -459,11 +569,20 @@ def topk_recall_threshold(
     out_i = torch.gather(ids, 1, fin.indices)
 
     # 5. fallback for underflowed queries (non-Gaussian tails / theta high)
-    bad = (counts < k) | (counts > cap)
+    if owner is None:
+        bad = (counts < k) | (counts > cap)
+    else:
+        # an owner with fewer than k rows legitimately underfills: those
+        # queries are done once every owned row is a candidate
+        bad = (counts < n_owned.clamp_max(k)) | (counts > cap)
     if bool(bad.any()):
         rows = bad.nonzero(as_tuple=True)[0]
-        k2f = min(4 * k, X.shape[0])
-        fb_s, fb_i = topk_recall(Q[rows].contiguous(), X, k2f)
+        k2f = min(4 * k, 32, X.shape[0])  # the direct kernel's k bound
+        if owner is None:
+            fb_s, fb_i = topk_recall(Q[rows].contiguous(), X, k2f)
+        else:
+            fb_s, fb_i = topk_recall(Q[rows].contiguous(), X, k2f, owner=owner,
+                                     qowner=qowner[rows].contiguous())
         # exact fp32 rescore (+ salience weight) so fallback rows report
         # the same score definition as the main path
         fb_g = fb_i.long().clamp_min(0)
@@ -511,8 +630,16 @@ def topk_recall_threshold_banded(
     if hot_X is None:
         hot_X = X[hot_idx.long()]
     hot = torch.matmul(Q, hot_X.T).float() * salience[hot_idx.long()]
+    owner, qowner = _owner_args(kw.get("owner"), kw.get("qowner"))
+    if owner is not None:
+        # hot band under the owner filter: foreign rows never reach its top-k
+        qo = qowner.long().unsqueeze(1)
+        eligible = (qo < 0) | (owner[hot_idx.long()].long().unsqueeze(0) == qo)
+        hot = torch.where(eligible, hot, torch.full_like(hot, -1e30))
     hs, hsel = torch.topk(hot, min(k, nh), dim=1)
     hi = hot_idx[hsel.reshape(-1)].reshape(hsel.shape).to(torch.int32)
+    if owner is not None:
+        hi = torch.where(hs > -1e29, hi, torch.full_like(hi, -1))
 
     cs, ci = topk_recall_threshold(Q, X, k, salience=salience, **kw)
     if is_hot is None:
@@ -520,6 +647,10 @@ def topk_recall_threshold_banded(
         is_hot[hot_idx.long()] = True
     dup = is_hot[ci.long().clamp_min(0)]
     cs = torch.where(dup, torch.full_like(cs, -1e30), cs)
+    if owner is not None:
+        # an owner short of k rows fills its tail from masked slots: they
+        # must not carry the id of a row the hot band already returned
+        ci = torch.where(dup, torch.full_like(ci, -1), ci)
 
     all_s = torch.cat([hs, cs], dim=1)
     all_i = torch.cat([hi, ci], dim=1)

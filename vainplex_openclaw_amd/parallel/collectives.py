@@ -48,6 +48,17 @@ def allgather_queries(feats: torch.Tensor, world: int) -> torch.Tensor:
     return out
 
 
+def allgather_owners(qowner: torch.Tensor, world: int) -> torch.Tensor:
+    """[B] int32 query owners per rank -> [world*B], in the row order of
+    allgather_queries (rank-major), so gathered owner i belongs to gathered
+    query i."""
+    if world <= 1:
+        return qowner
+    out = torch.empty(world * qowner.shape[0], dtype=qowner.dtype, device=qowner.device)
+    dist.all_gather_into_tensor(out, qowner.contiguous())
+    return out
+
+
 def globalize_ids(ids: torch.Tensor, rank: int, shard_rows: int) -> torch.Tensor:
     """Shard-local row ids -> global ids (invalid -1 slots preserved)."""
     out = ids + rank * shard_rows

@@ -87,6 +87,10 @@ class PipelineConfig:
     # overfetch under skewed salience (ops.gpu.topk_recall_threshold_banded)
     hot_frac: float = 0.002
     band_refresh_steps: int = 64
+    # per-agent recall isolation: every index row gets a (synthetic) owner
+    # agent and a message recalls only rows of its own agent; the filter
+    # runs inside the recall kernels (threshold, threshold_banded, direct)
+    recall_isolation: bool = False
 
 
 class StageProfiler:
@@ -183,6 +187,22 @@ class FirewallPipeline:
 
             # salience state: recall strength + decay (Membrane semantics)
             self.salience = torch.ones(cfg.index_size, device=self.device)
+
+            # recall isolation: synthetic row owners, uniform over the
+            # agents, from a generator of their own so the index contents
+            # do not depend on the flag
+            self.index_owner = None
+            self.owner_counts = None
+            if cfg.recall_isolation:
+                if cfg.recall_mode == "two_stage":
+                    raise ValueError("recall_isolation: two_stage recall has no owner filter")
+                ogen = torch.Generator(device="cuda")
+                ogen.manual_seed(cfg.seed * 104729 + 17 + rank)
+                self.index_owner = torch.randint(
+                    0, cfg.n_agents, (cfg.index_size,), generator=ogen,
+                    dtype=torch.int32, device=self.device)
+                self.owner_counts = torch.bincount(
+                    self.index_owner.long(), minlength=cfg.n_agents)
 
             # hot-band caches for threshold_banded recall; refreshed every
             # band_refresh_steps as reinforcement reshapes the salience
@@ -327,28 +347,35 @@ class FirewallPipeline:
         # every candidate's salience lives on its owning shard.
         sal = self.salience if cfg.salience_weighting else None
 
-        def local_recall(queries):
+        own = {}
+        if self.index_owner is not None:
+            own = {"owner": self.index_owner, "owner_counts": self.owner_counts}
+
+        def local_recall(queries, qowner=None):
+            if qowner is not None:
+                own["qowner"] = qowner
             if cfg.recall_mode == "threshold_banded" and sal is not None:
                 if self._steps_done and self._steps_done % cfg.band_refresh_steps == 0:
                     self._refresh_hot_band()
                 return g.topk_recall_threshold_banded(
                     queries, self.index, cfg.topk, salience=sal,
                     hot_idx=self.hot_idx, hot_X=self.hot_X, is_hot=self.is_hot,
-                    X8=self.index8, mx=cfg.recall_mx, X4=self.index4,
+                    X8=self.index8, mx=cfg.recall_mx, X4=self.index4, **own,
                 )
             if cfg.recall_mode in ("threshold", "threshold_banded"):
                 return g.topk_recall_threshold(
                     queries, self.index, cfg.topk, X8=self.index8,
-                    mx=cfg.recall_mx, X4=self.index4, salience=sal
+                    mx=cfg.recall_mx, X4=self.index4, salience=sal, **own
                 )
             if cfg.recall_mode == "two_stage" and self.index8 is not None:
                 return g.topk_recall_two_stage(queries, self.index, self.index8,
                                                cfg.topk, salience=sal)
+            direct_own = {k_: v for k_, v in own.items() if k_ != "owner_counts"}
             if sal is None:
-                return g.topk_recall(queries, self.index, cfg.topk)
+                return g.topk_recall(queries, self.index, cfg.topk, **direct_own)
             # direct mode: overfetch 2k by cosine, weight, re-top-k
             k2 = min(2 * cfg.topk, self.index.shape[0])
-            s0, i0 = g.topk_recall(queries, self.index, k2)
+            s0, i0 = g.topk_recall(queries, self.index, k2, **direct_own)
             w = s0 * sal[i0.long().clamp_min(0)]
             w = torch.where(i0 < 0, torch.full_like(w, -1e30), w)
             top = torch.topk(w, cfg.topk, dim=1)
@@ -356,13 +383,17 @@ class FirewallPipeline:
 
         if self.world_size > 1 and torch.distributed.is_initialized():
             q_all = coll.allgather_queries(feats, self.world_size)
-            scores, ids = local_recall(q_all)
+            qo_all = None
+            if self.index_owner is not None:
+                qo_all = coll.allgather_owners(agent_idx.to(torch.int32), self.world_size)
+            scores, ids = local_recall(q_all, qo_all)
             ids = coll.globalize_ids(ids.to(torch.int32), self.rank, cfg.index_size)
             recall_scores, recall_ids = coll.merge_topk_candidates(
                 scores, ids, self.rank, B, self.world_size, cfg.topk
             )
         else:
-            recall_scores, recall_ids = local_recall(feats)
+            recall_scores, recall_ids = local_recall(
+                feats, agent_idx.to(torch.int32) if self.index_owner is not None else None)
 
         # salience reinforcement + decay (Membrane recall semantics)
         if self.world_size > 1:
