@@ -75,6 +75,9 @@ __global__ void fact_probe_kernel(const uint8_t*, const int32_t*,
                                   const unsigned long long*, const unsigned long long*,
                                   const unsigned long long*, const unsigned long long*,
                                   int, int32_t*, int32_t*, int);
+__global__ void fp4_quantize_append_kernel(const uint16_t*, const int32_t*, int, long long,
+                                           int, long long, uint16_t*, uint8_t*, uint8_t*,
+                                           int32_t*, const int32_t*, float*, float);
 struct AuditRecord64;
 __global__ void audit_pack_kernel(const int8_t*, const float*, const unsigned long long*,
                                   const unsigned long long*, const int32_t*, const float*,
@@ -564,6 +567,125 @@ std::vector<torch::Tensor> topk_scan_threshold(torch::Tensor Q, torch::Tensor X,
   return {cand_s, cand_i, counts};
 }
 
+// -- fused MXFP4 quantize / index append (csrc/fp4_quantize.hip) ----------
+
+static bool aligned16(const torch::Tensor& t) {
+  return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0;
+}
+
+static void launch_fp4_quantize_append(
+    const torch::Tensor& feats, const int32_t* src_idx, long long n, long long dst_row0,
+    uint16_t* index_dst, uint8_t* x4, uint8_t* xs, int32_t* owner_dst,
+    const int32_t* owner_src, float* salience_dst, float salience_init) {
+  if (n == 0) return;
+  int D = feats.size(1);
+  long long items = n * (D / 16);
+  long long blocks = (items + 255) / 256;
+  // memory-bound: cap the grid and stride the rest
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  hipLaunchKernelGGL(fp4_quantize_append_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                     cur_stream(),
+                     reinterpret_cast<const uint16_t*>(feats.data_ptr()), src_idx,
+                     (int)feats.size(0), n, D, dst_row0, index_dst, x4, xs, owner_dst,
+                     owner_src, salience_dst, salience_init);
+}
+
+static void check_fp4_dst(const torch::Tensor& X4, const torch::Tensor& XS, long long rows,
+                          int D) {
+  CHECK_GPU(X4); CHECK_CONTIG(X4); CHECK_GPU(XS); CHECK_CONTIG(XS);
+  TORCH_CHECK(X4.dtype() == torch::kUInt8 && XS.dtype() == torch::kUInt8,
+              "X4/XS must be uint8");
+  TORCH_CHECK(X4.dim() == 2 && XS.dim() == 2 && X4.size(0) == rows && XS.size(0) == rows &&
+              X4.size(1) == D / 2 && XS.size(1) == D / 32,
+              "X4/XS must be [rows, D/2] and [rows, D/32]");
+  TORCH_CHECK(aligned16(X4) && aligned16(XS), "X4/XS must be 16-byte aligned");
+}
+
+std::vector<torch::Tensor> quantize_fp4_mx(torch::Tensor X,
+                                           c10::optional<torch::Tensor> out4,
+                                           c10::optional<torch::Tensor> outs) {
+  // bf16 [n, D] -> (packed e2m1 [n, D/2], e8m0 scales [n, D/32]), bit-exact
+  // with ops.gpu.to_fp4_mx; out4/outs let a caller fill preallocated rows
+  CHECK_GPU(X); CHECK_CONTIG(X);
+  TORCH_CHECK(X.dtype() == torch::kBFloat16 && X.dim() == 2, "X must be bf16 [n, D]");
+  long long n = X.size(0);
+  int D = X.size(1);
+  TORCH_CHECK(D % 128 == 0 && D <= 2048, "fp4 quantize needs D%128==0, D<=2048");
+  TORCH_CHECK(n < (1LL << 31), "X has too many rows");
+  TORCH_CHECK(aligned16(X), "X must be 16-byte aligned");
+  TORCH_CHECK(out4.has_value() == outs.has_value(), "out4 and outs go together");
+  auto u8opts = torch::dtype(torch::kUInt8).device(X.device());
+  auto X4 = out4.has_value() ? *out4 : torch::empty({n, D / 2}, u8opts);
+  auto XS = outs.has_value() ? *outs : torch::empty({n, D / 32}, u8opts);
+  check_fp4_dst(X4, XS, n, D);
+  launch_fp4_quantize_append(X, nullptr, n, 0, nullptr, X4.data_ptr<uint8_t>(),
+                             XS.data_ptr<uint8_t>(), nullptr, nullptr, nullptr, 0.f);
+  return {X4, XS};
+}
+
+void index_append(torch::Tensor feats, c10::optional<torch::Tensor> src_idx,
+                  int64_t dst_row0, torch::Tensor index,
+                  c10::optional<torch::Tensor> X4, c10::optional<torch::Tensor> XS,
+                  c10::optional<torch::Tensor> owner_dst,
+                  c10::optional<torch::Tensor> owner_src,
+                  c10::optional<torch::Tensor> salience_dst, double salience_init) {
+  // rows dst_row0 + i of the live index <- feats[src_idx[i]] (or feats[i]):
+  // bf16 copy, fp4 codes + scales, owner and salience in one launch
+  CHECK_GPU(feats); CHECK_CONTIG(feats); CHECK_GPU(index); CHECK_CONTIG(index);
+  TORCH_CHECK(feats.dtype() == torch::kBFloat16 && feats.dim() == 2,
+              "feats must be bf16 [m, D]");
+  TORCH_CHECK(index.dtype() == torch::kBFloat16 && index.dim() == 2,
+              "index must be bf16 [cap, D]");
+  long long m = feats.size(0), cap = index.size(0);
+  int D = feats.size(1);
+  TORCH_CHECK(index.size(1) == D, "feats and index differ in D");
+  TORCH_CHECK(D % 128 == 0 && D <= 2048, "index append needs D%128==0, D<=2048");
+  TORCH_CHECK(m < (1LL << 31), "feats has too many rows");
+  TORCH_CHECK(aligned16(feats) && aligned16(index), "feats/index must be 16-byte aligned");
+  TORCH_CHECK(feats.device() == index.device(), "feats and index on different devices");
+  long long n = m;
+  const int32_t* sp = nullptr;
+  if (src_idx.has_value()) {
+    CHECK_GPU((*src_idx)); CHECK_CONTIG((*src_idx));
+    TORCH_CHECK(src_idx->dtype() == torch::kInt32 && src_idx->dim() == 1,
+                "src_idx must be int32 [n]");
+    n = src_idx->numel();
+    sp = src_idx->data_ptr<int32_t>();
+  }
+  TORCH_CHECK(dst_row0 >= 0 && dst_row0 + n <= cap,
+              "index append window [", dst_row0, ", ", dst_row0 + n, ") exceeds capacity ", cap);
+  TORCH_CHECK(X4.has_value() == XS.has_value(), "X4 and XS go together");
+  uint8_t* x4p = nullptr; uint8_t* xsp = nullptr;
+  if (X4.has_value()) {
+    check_fp4_dst(*X4, *XS, cap, D);
+    x4p = X4->data_ptr<uint8_t>();
+    xsp = XS->data_ptr<uint8_t>();
+  }
+  TORCH_CHECK(owner_dst.has_value() == owner_src.has_value(),
+              "owner_dst and owner_src go together");
+  int32_t* odp = nullptr; const int32_t* osp = nullptr;
+  if (owner_dst.has_value()) {
+    CHECK_GPU((*owner_dst)); CHECK_CONTIG((*owner_dst));
+    CHECK_GPU((*owner_src)); CHECK_CONTIG((*owner_src));
+    TORCH_CHECK(owner_dst->dtype() == torch::kInt32 && owner_src->dtype() == torch::kInt32,
+                "owners must be int32");
+    TORCH_CHECK(owner_dst->dim() == 1 && owner_dst->numel() == cap, "owner_dst must be [cap]");
+    TORCH_CHECK(owner_src->dim() == 1 && owner_src->numel() == m, "owner_src must be [m]");
+    odp = owner_dst->data_ptr<int32_t>();
+    osp = owner_src->data_ptr<int32_t>();
+  }
+  float* sdp = nullptr;
+  if (salience_dst.has_value()) {
+    CHECK_GPU((*salience_dst)); CHECK_CONTIG((*salience_dst));
+    TORCH_CHECK(salience_dst->dtype() == torch::kFloat32 && salience_dst->dim() == 1 &&
+                salience_dst->numel() == cap, "salience_dst must be f32 [cap]");
+    sdp = salience_dst->data_ptr<float>();
+  }
+  launch_fp4_quantize_append(feats, sp, n, dst_row0,
+                             reinterpret_cast<uint16_t*>(index.data_ptr()), x4p, xsp, odp,
+                             osp, sdp, (float)salience_init);
+}
+
 void register_host_envelope(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -665,6 +787,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Q4"), py::arg("QS"), py::arg("X4"), py::arg("XS"),
         py::arg("theta"), py::arg("xowner"), py::arg("qowner"), py::arg("cap"),
         py::arg("n_swaths"));
+  m.def("quantize_fp4_mx", &quantize_fp4_mx,
+        "fused bf16 -> MXFP4 (fragment order) quantize, bit-exact with to_fp4_mx",
+        py::arg("X"), py::arg("out4") = c10::nullopt, py::arg("outs") = c10::nullopt);
+  m.def("index_append", &index_append,
+        "append rows to the live recall index: bf16 + fp4 + scales + owner + salience",
+        py::arg("feats"), py::arg("src_idx"), py::arg("dst_row0"), py::arg("index"),
+        py::arg("X4") = c10::nullopt, py::arg("XS") = c10::nullopt,
+        py::arg("owner_dst") = c10::nullopt, py::arg("owner_src") = c10::nullopt,
+        py::arg("salience_dst") = c10::nullopt, py::arg("salience_init") = 1.0);
   m.def("edit_distance", [](torch::Tensor bytes, torch::Tensor offsets) {
     // batched Levenshtein over string PAIRS: offsets has 2*n+1 entries;
     // pair i = strings (2i, 2i+1) in the packed byte buffer

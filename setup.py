@@ -21,6 +21,7 @@ SOURCES = [
     "csrc/encoder.hip",
     "csrc/gemm_nt.hip",
     "csrc/topk_recall.hip",
+    "csrc/fp4_quantize.hip",
     "csrc/firewall.hip",
     "csrc/edit_distance.hip",
     "csrc/fact_probe.hip",

@@ -311,6 +311,90 @@ def to_fp4_mx(x: torch.Tensor, chunk_rows: int = 1_048_576) -> Tuple[torch.Tenso
     return out4, outs
 
 
+def fp4_mx_spec(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The contract of csrc/fp4_quantize.hip written down in torch: the
+    same output as to_fp4_mx, bit for bit on finite input, from integer
+    rules only (no log2, no permutation gather). Device agnostic.
+
+    Per 128-element chunk c and group g in 0..3 the group's 32 elements
+    are c*128 + s + [0,16) and c*128 + s + 32 + [0,16), s = (g&1)*64 +
+    (g>>1)*16; their codes fill bytes c*64 + g*16 + [0,16) (low nibble =
+    even position) and their scale is XS[:, c*4 + g].
+
+    Scale: the group max as a bf16 bit pattern has exponent field E and
+    mantissa M. max == 0 -> e = 0; else e = E - 129 if M <= 64 (max <=
+    1.5 * 2^(E-127)) else E - 128, clamped below at -127 (which also
+    covers a subnormal max, E = 0). Scale byte = e + 127.
+    Code: y = v * 2^-e (exact); magnitude code = number of e2m1 midpoints
+    strictly below |y|; sign bit iff y < 0 in fp32."""
+    N, D = x.shape
+    assert D % 128 == 0 and x.dtype == torch.bfloat16
+    # element c*128 + (g&1)*64 + half*32 + (g>>1)*16 + i: split the chunk
+    # into (g&1, half, g>>1, i) and reorder to (g>>1, g&1, half, i), i.e.
+    # group-major with 32 consecutive elements per group
+    def grouped(t):
+        t = t.view(N, D // 128, 2, 2, 2, 16).permute(0, 1, 4, 2, 3, 5)
+        return t.reshape(N, D // 32, 32)
+
+    x = x.contiguous()
+    b = grouped(x.view(torch.int16).to(torch.int32))
+    v = grouped(x.float())
+    amax = (b & 0x7FFF).amax(dim=2)
+    E, M = amax >> 7, amax & 0x7F
+    e = torch.where(M <= 64, E - 129, E - 128).clamp_min(-127)
+    e = torch.where(amax == 0, torch.zeros_like(e), e)
+    outs = (e + 127).to(torch.uint8)
+    inv = ((127 - e) << 23).to(torch.int32).view(torch.float32)  # 2^-e
+    y = v * inv.unsqueeze(2)
+    a = y.abs()
+    code = torch.zeros_like(b)
+    for mid in _E2M1_MIDPOINTS:
+        code += (a > mid).to(torch.int32)
+    code |= (y < 0).to(torch.int32) << 3
+    code = code.view(N, D)
+    out4 = (code[:, 0::2] | (code[:, 1::2] << 4)).to(torch.uint8)
+    return out4, outs
+
+
+def quantize_fp4_mx(
+    x: torch.Tensor,
+    out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """to_fp4_mx as ONE kernel launch (csrc/fp4_quantize.hip): bf16 [n, D]
+    read once, codes and scales written once, no fp32 temporaries. Output
+    is bit-for-bit to_fp4_mx(x). `out` = (X4 [n, D/2], XS [n, D/32])
+    fills preallocated contiguous rows in place of allocating."""
+    x = x.contiguous()
+    if out is None:
+        x4, xs = ext().quantize_fp4_mx(x)
+    else:
+        x4, xs = ext().quantize_fp4_mx(x, out[0], out[1])
+    return x4, xs
+
+
+def index_append(
+    feats: torch.Tensor,
+    src_idx: Optional[torch.Tensor],
+    dst_row0: int,
+    index: torch.Tensor,
+    X4: Optional[torch.Tensor] = None,
+    XS: Optional[torch.Tensor] = None,
+    owner_dst: Optional[torch.Tensor] = None,
+    owner_src: Optional[torch.Tensor] = None,
+    salience_dst: Optional[torch.Tensor] = None,
+    salience_init: float = 1.0,
+) -> None:
+    """Append rows to a live recall index in one launch: row dst_row0 + i
+    of `index` (bf16 [cap, D]), of the MXFP4 pair X4/XS, of `owner_dst`
+    and of `salience_dst` receives feats[src_idx[i]] (feats[i] when
+    src_idx is None), its fp4 codes and scales (as to_fp4_mx would build
+    them), owner_src[src_idx[i]] and salience_init. Every destination
+    except `index` is optional. A src_idx entry outside feats leaves its
+    destination row untouched; dst_row0 + n past the capacity raises."""
+    ext().index_append(feats, src_idx, int(dst_row0), index, X4, XS,
+                       owner_dst, owner_src, salience_dst, float(salience_init))
+
+
 def topk_recall_fp8(Q8: torch.Tensor, X8: torch.Tensor, k: int, n_swaths: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """Stage-1 fp8 scan: candidate ids ranked by e4m3 cosine (csrc
     topk_recall_fp8_kernel). Inputs are uint8 views of e4m3 bytes."""
@@ -513,7 +597,8 @@ def topk_recall_threshold(
     # 2. fixed-threshold scan
     if use_fp4 and q4 and D <= 1024:
         # both operands MXFP4: scores carry no static prescale
-        Q4, QS = to_fp4_mx(Q)
+        # (one fused launch, bit-exact with to_fp4_mx)
+        Q4, QS = quantize_fp4_mx(Q)
         if owner is None:
             cs, ci, counts = ext().topk_scan_threshold_fp4x4(
                 Q4, QS, X4[0], X4[1], theta.contiguous(), cap, 0)

@@ -23,6 +23,9 @@ messages:
      the reference's risk weights / verdict precedence / trust formula
   7. audit: 64-B records packed on GPU, SHA-256 leaves + Merkle root
      (csrc/sha256_merkle.hip)
+  8. (cfg.ingest) Membrane ingest (csrc/fp4_quantize.hip): the messages
+     that were not denied are appended to the live index shard — bf16 row,
+     MXFP4 codes + scales, owner, salience — and later steps recall them
 
 Multi-GPU (one process per GPU, torch.distributed over RCCL/xGMI):
 the index is sharded across ranks; recall queries are all-gathered so
@@ -47,6 +50,8 @@ from ..ops import gpu as g
 from ..ops import pattern_sets
 from ..parallel import collectives as coll
 from .synth import SynthBatch
+
+V_DENY = 3  # csrc/firewall.hip verdict code
 
 
 @dataclass
@@ -91,6 +96,12 @@ class PipelineConfig:
     # agent and a message recalls only rows of its own agent; the filter
     # runs inside the recall kernels (threshold, threshold_banded, direct)
     recall_isolation: bool = False
+    # online memory ingest: every step appends its non-denied messages to
+    # the recall index (csrc/fp4_quantize.hip, one launch) so later steps
+    # recall them; ingest_capacity = spare rows per shard, append-only,
+    # messages past a full index are counted in ingest_dropped
+    ingest: bool = False
+    ingest_capacity: int = 0
 
 
 class StageProfiler:
@@ -151,7 +162,23 @@ class FirewallPipeline:
             chunk = 1_000_000
             gen = torch.Generator(device="cuda")
             gen.manual_seed(cfg.seed * 7919 + rank)
-            self.index = torch.empty(cfg.index_size, cfg.dim, dtype=torch.bfloat16, device=self.device)
+            # live rows are the [:n_rows] prefix of every index buffer;
+            # ingest allocates ingest_capacity spare rows behind them
+            fp4_index = cfg.recall_fp4 and cfg.dim % 128 == 0 \
+                and cfg.recall_mode in ("threshold", "threshold_banded")
+            fp8_index = not fp4_index and cfg.recall_fp8 \
+                and cfg.recall_mode in ("two_stage", "threshold", "threshold_banded")
+            if cfg.ingest and fp8_index:
+                raise ValueError("ingest: no append path for the e4m3 index copy "
+                                 "(two_stage, or threshold recall without recall_fp4)")
+            if cfg.ingest and cfg.dim % 128 != 0:
+                raise ValueError("ingest: the append kernel needs dim % 128 == 0")
+            self.n_rows = cfg.index_size
+            self.capacity = cfg.index_size + (max(0, cfg.ingest_capacity) if cfg.ingest else 0)
+            self.ingest_dropped = 0
+            cap = self.capacity
+            self.index = torch.empty(cap, cfg.dim, dtype=torch.bfloat16, device=self.device)
+            self.index[cfg.index_size:].zero_()
             for i in range(0, cfg.index_size, chunk):
                 n = min(chunk, cfg.index_size - i)
                 x = torch.randn(n, cfg.dim, generator=gen, dtype=torch.float32, device=self.device)
@@ -164,20 +191,16 @@ class FirewallPipeline:
             # e4m3 copy serves the two_stage mode and the fp8/MX scans.
             self.index8 = None
             self.index4 = None
-            if cfg.recall_fp4 and cfg.recall_mode in ("threshold", "threshold_banded") \
-                    and cfg.dim % 128 == 0:
-                x4 = torch.empty(cfg.index_size, cfg.dim // 2, dtype=torch.uint8,
-                                 device=self.device)
-                xs = torch.empty(cfg.index_size, cfg.dim // 32, dtype=torch.uint8,
-                                 device=self.device)
-                for i in range(0, cfg.index_size, chunk):
-                    n = min(chunk, cfg.index_size - i)
-                    c4, cs = g.to_fp4_mx(self.index[i : i + n])
-                    x4[i : i + n] = c4
-                    xs[i : i + n] = cs
+            if fp4_index:
+                x4 = torch.empty(cap, cfg.dim // 2, dtype=torch.uint8, device=self.device)
+                xs = torch.empty(cap, cfg.dim // 32, dtype=torch.uint8, device=self.device)
+                # one launch, written in place: no chunking, no temporaries
+                n0 = cfg.index_size
+                g.quantize_fp4_mx(self.index[:n0], out=(x4[:n0], xs[:n0]))
+                x4[n0:].zero_()
+                xs[n0:].zero_()
                 self.index4 = (x4, xs)
-            elif cfg.recall_fp8 and cfg.recall_mode in ("two_stage", "threshold",
-                                                        "threshold_banded"):
+            elif fp8_index:
                 self.index8 = torch.empty(
                     cfg.index_size, cfg.dim, dtype=torch.uint8, device=self.device
                 )
@@ -186,7 +209,7 @@ class FirewallPipeline:
                     self.index8[i : i + n] = g.to_fp8_bytes(self.index[i : i + n])
 
             # salience state: recall strength + decay (Membrane semantics)
-            self.salience = torch.ones(cfg.index_size, device=self.device)
+            self.salience = torch.ones(cap, device=self.device)
 
             # recall isolation: synthetic row owners, uniform over the
             # agents, from a generator of their own so the index contents
@@ -198,11 +221,12 @@ class FirewallPipeline:
                     raise ValueError("recall_isolation: two_stage recall has no owner filter")
                 ogen = torch.Generator(device="cuda")
                 ogen.manual_seed(cfg.seed * 104729 + 17 + rank)
-                self.index_owner = torch.randint(
+                self.index_owner = torch.full((cap,), -1, dtype=torch.int32, device=self.device)
+                self.index_owner[:cfg.index_size] = torch.randint(
                     0, cfg.n_agents, (cfg.index_size,), generator=ogen,
                     dtype=torch.int32, device=self.device)
                 self.owner_counts = torch.bincount(
-                    self.index_owner.long(), minlength=cfg.n_agents)
+                    self.index_owner[:cfg.index_size].long(), minlength=cfg.n_agents)
 
             # hot-band caches for threshold_banded recall; refreshed every
             # band_refresh_steps as reinforcement reshapes the salience
@@ -261,11 +285,39 @@ class FirewallPipeline:
         (threshold_banded mode). Cheap relative to a step: topk over the
         salience vector + a nh-row gather."""
         cfg = self.cfg
-        nh = max(1, int(cfg.index_size * cfg.hot_frac))
-        self.hot_idx = torch.topk(self.salience, min(nh, cfg.index_size)).indices
+        n = self.n_rows
+        nh = max(1, int(n * cfg.hot_frac))
+        self.hot_idx = torch.topk(self.salience[:n], min(nh, n)).indices
         self.hot_X = self.index[self.hot_idx]
-        self.is_hot = torch.zeros(cfg.index_size, dtype=torch.bool, device=self.device)
+        self.is_hot = torch.zeros(self.capacity, dtype=torch.bool, device=self.device)
         self.is_hot[self.hot_idx] = True
+
+    def _ingest(self, feats: torch.Tensor, verdict: torch.Tensor,
+                agent_idx: torch.Tensor) -> None:
+        """Remember this step's messages: append every feature row whose
+        verdict is not deny to the live index (bf16 row, fp4 codes and
+        scales, owner, salience 1.0) with one g.index_append launch. The
+        nonzero() is the step's one host read (the kept count). Append
+        only: rows that do not fit are counted in ingest_dropped."""
+        src = torch.nonzero(verdict != V_DENY).flatten().to(torch.int32)
+        kept = int(src.numel())
+        take = min(kept, self.capacity - self.n_rows)
+        self.ingest_dropped += kept - take
+        if take == 0:
+            return
+        src = src[:take]
+        x4, xs = self.index4 if self.index4 is not None else (None, None)
+        owner_src = None
+        if self.index_owner is not None:
+            owner_src = agent_idx.to(torch.int32)
+        g.index_append(
+            feats, src, self.n_rows, self.index, x4, xs,
+            owner_dst=self.index_owner, owner_src=owner_src,
+            salience_dst=self.salience, salience_init=1.0)
+        if self.owner_counts is not None:
+            owners = owner_src[src.long()].long()
+            self.owner_counts.index_add_(0, owners, torch.ones_like(owners))
+        self.n_rows += take
 
     # -- input staging -----------------------------------------------------
     def stage(self, batch: SynthBatch) -> Dict[str, torch.Tensor]:
@@ -345,11 +397,17 @@ class FirewallPipeline:
         # * decayed salience; candidates overfetched by raw cosine, exact
         # rescore applies the weight). Weighting happens rank-locally:
         # every candidate's salience lives on its owning shard.
-        sal = self.salience if cfg.salience_weighting else None
+        # the live rows: contiguous [:n_rows] prefix views (the whole
+        # buffers unless ingest reserved spare rows behind them)
+        n_live = self.n_rows
+        index = self.index[:n_live]
+        index4 = None if self.index4 is None else \
+            (self.index4[0][:n_live], self.index4[1][:n_live])
+        sal = self.salience[:n_live] if cfg.salience_weighting else None
 
         own = {}
         if self.index_owner is not None:
-            own = {"owner": self.index_owner, "owner_counts": self.owner_counts}
+            own = {"owner": self.index_owner[:n_live], "owner_counts": self.owner_counts}
 
         def local_recall(queries, qowner=None):
             if qowner is not None:
@@ -358,24 +416,24 @@ class FirewallPipeline:
                 if self._steps_done and self._steps_done % cfg.band_refresh_steps == 0:
                     self._refresh_hot_band()
                 return g.topk_recall_threshold_banded(
-                    queries, self.index, cfg.topk, salience=sal,
-                    hot_idx=self.hot_idx, hot_X=self.hot_X, is_hot=self.is_hot,
-                    X8=self.index8, mx=cfg.recall_mx, X4=self.index4, **own,
+                    queries, index, cfg.topk, salience=sal,
+                    hot_idx=self.hot_idx, hot_X=self.hot_X, is_hot=self.is_hot[:n_live],
+                    X8=self.index8, mx=cfg.recall_mx, X4=index4, **own,
                 )
             if cfg.recall_mode in ("threshold", "threshold_banded"):
                 return g.topk_recall_threshold(
-                    queries, self.index, cfg.topk, X8=self.index8,
-                    mx=cfg.recall_mx, X4=self.index4, salience=sal, **own
+                    queries, index, cfg.topk, X8=self.index8,
+                    mx=cfg.recall_mx, X4=index4, salience=sal, **own
                 )
             if cfg.recall_mode == "two_stage" and self.index8 is not None:
-                return g.topk_recall_two_stage(queries, self.index, self.index8,
+                return g.topk_recall_two_stage(queries, index, self.index8,
                                                cfg.topk, salience=sal)
             direct_own = {k_: v for k_, v in own.items() if k_ != "owner_counts"}
             if sal is None:
-                return g.topk_recall(queries, self.index, cfg.topk, **direct_own)
+                return g.topk_recall(queries, index, cfg.topk, **direct_own)
             # direct mode: overfetch 2k by cosine, weight, re-top-k
-            k2 = min(2 * cfg.topk, self.index.shape[0])
-            s0, i0 = g.topk_recall(queries, self.index, k2, **direct_own)
+            k2 = min(2 * cfg.topk, index.shape[0])
+            s0, i0 = g.topk_recall(queries, index, k2, **direct_own)
             w = s0 * sal[i0.long().clamp_min(0)]
             w = torch.where(i0 < 0, torch.full_like(w, -1e30), w)
             top = torch.topk(w, cfg.topk, dim=1)
@@ -387,7 +445,8 @@ class FirewallPipeline:
             if self.index_owner is not None:
                 qo_all = coll.allgather_owners(agent_idx.to(torch.int32), self.world_size)
             scores, ids = local_recall(q_all, qo_all)
-            ids = coll.globalize_ids(ids.to(torch.int32), self.rank, cfg.index_size)
+            # shard id stride = the shard's capacity (== index_size without ingest)
+            ids = coll.globalize_ids(ids.to(torch.int32), self.rank, self.capacity)
             recall_scores, recall_ids = coll.merge_topk_candidates(
                 scores, ids, self.rank, B, self.world_size, cfg.topk
             )
@@ -398,7 +457,7 @@ class FirewallPipeline:
         # salience reinforcement + decay (Membrane recall semantics)
         if self.world_size > 1:
             flat_local = coll.local_shard_ids(
-                recall_ids.reshape(-1), self.rank, cfg.index_size
+                recall_ids.reshape(-1), self.rank, self.capacity
             )
         else:
             flat_local = recall_ids.reshape(-1)
@@ -406,7 +465,7 @@ class FirewallPipeline:
         # organic decay per step + recall reinforcement toward 1.0
         # (membrane/store.py: decayed_salience floor MIN_SALIENCE=0.01,
         # reinforce s += RECALL_BOOST(0.25) * (1 - s), cap 1.0)
-        self.salience.mul_(0.9999).clamp_(min=0.01)
+        self.salience[:n_live].mul_(0.9999).clamp_(min=0.01)
         uniq = torch.unique(flat_local.long())
         if uniq.numel():
             su = self.salience[uniq]
@@ -455,6 +514,10 @@ class FirewallPipeline:
                 torch.zeros(B, dtype=torch.int8, device=self.device),
             ),
         )
+
+        if cfg.ingest:
+            prof.mark("ingest")
+            self._ingest(feats, verdict, agent_idx)
 
         prof.mark("end")
         self.batch_seq += 1
