@@ -52,6 +52,9 @@ __global__ void topk_scan_fp4_v5_kernel(const uint8_t*, const uint8_t*, const ui
 __global__ void topk_scan_fp4_v7_kernel(const uint8_t*, const uint8_t*, const uint8_t*,
                                         const uint8_t*, int, int, int, int, int,
                                         float*, int32_t*, const float*, int32_t*, int);
+__global__ void topk_scan_fp4_v9_kernel(const uint8_t*, const uint8_t*, const uint8_t*,
+                                        const uint8_t*, int, int, int, int, int,
+                                        float*, int32_t*, const float*, int32_t*, int);
 __global__ void topk_scan_fp4_owned_kernel(const uint8_t*, const uint8_t*, const uint8_t*,
                                            const uint8_t*, int, int, int, int, int,
                                            float*, int32_t*, const float*, int32_t*, int,
@@ -419,7 +422,7 @@ static std::vector<torch::Tensor> fp4x4_scan(
     bool scan_only, const torch::Tensor* xowner, const torch::Tensor* qowner) {
   // both operands MXFP4 (csrc topk_scan_fp4_kernel); scores at x1.
   // variant_arg: -1 = environment/default, 0 = v1, 1 = v2, 2 = v3,
-  // 4 = v5, 7 = v7. scan_only runs the K-loops without the epilogue
+  // 4 = v5, 7 = v7, 9 = v9. scan_only runs the K-loops without the epilogue
   // (k = -1) for epilogue-share attribution.
   CHECK_GPU(Q4); CHECK_CONTIG(Q4); CHECK_GPU(QS); CHECK_CONTIG(QS);
   CHECK_GPU(X4); CHECK_CONTIG(X4); CHECK_GPU(XS); CHECK_CONTIG(XS);
@@ -431,19 +434,21 @@ static std::vector<torch::Tensor> fp4x4_scan(
   TORCH_CHECK(X4.size(1) == D / 2 && XS.size(0) == nx && XS.size(1) == D / 32);
   TORCH_CHECK(theta.numel() == nq && cap >= 32 && cap <= 4096);
   if (xowner != nullptr) check_owners(*xowner, *qowner, nx, nq);
-  // v7 (v3 + wave any-hit fast path, hoisted staging addresses, Q scale
-  // sheet staged once) is the default: bit-exact vs v1 and measured 11.0
-  // vs 15.4 ms at 4.2M x 4096. Env overrides for A/B.
+  // v9 (v7 + transposed scale sheets read as one dword per fragment per
+  // four pairs with the byte picked by op_sel, counted lgkmcnt per m) is
+  // the default: bit-exact vs v1 and measured 9.7 vs 11.0 ms at 4.2M x
+  // 4096. Env overrides for A/B; VAINPLEX_FP4_V7=1 is the way back to v7.
   static const int env_variant = [] {
     if (const char* e = getenv("VAINPLEX_FP4_V1"); e && e[0] == '1') return 0;
     if (const char* e = getenv("VAINPLEX_FP4_V2"); e && e[0] == '1') return 1;
     if (const char* e = getenv("VAINPLEX_FP4_V3"); e && e[0] == '1') return 2;
     if (const char* e = getenv("VAINPLEX_FP4_V5"); e && e[0] == '1') return 4;
-    return 7;
+    if (const char* e = getenv("VAINPLEX_FP4_V7"); e && e[0] == '1') return 7;
+    return 9;
   }();
   int variant = variant_arg < 0 ? env_variant : (int)variant_arg;
   TORCH_CHECK(variant == 0 || variant == 1 || variant == 2 || variant == 4 ||
-              variant == 7,
+              variant == 7 || variant == 9,
               "fp4x4 scan: unknown variant ", variant);
   int n_qblocks = (nq + 255) / 256;
   if (n_swaths <= 0) {
@@ -469,7 +474,8 @@ static std::vector<torch::Tensor> fp4x4_scan(
                        qowner->data_ptr<int32_t>());
     return {cand_s, cand_i, counts};
   }
-  auto kern = variant == 7 ? topk_scan_fp4_v7_kernel
+  auto kern = variant == 9 ? topk_scan_fp4_v9_kernel
+            : variant == 7 ? topk_scan_fp4_v7_kernel
             : variant == 4 ? topk_scan_fp4_v5_kernel
             : variant == 2 ? topk_scan_fp4_v3_kernel
             : variant == 1 ? topk_scan_fp4_v2_kernel : topk_scan_fp4_kernel;

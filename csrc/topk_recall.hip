@@ -1952,6 +1952,418 @@ topk_scan_fp4_v7_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
 }
 
 // ===========================================================================
+// fp4x4 threshold scan v9: v7 with the per-pair scale-byte reads gone.
+// v7 fetches a lane's 12 block scales of every pair with 12 ds_read_u8 from
+// row-major byte sheets; rows r, r+4, r+8, r+12 of a fragment share a bank
+// there (4-way). v9 keeps both sheets transposed in LDS, one dword per
+// (row, 4-pair group, kgrp) whose byte (pc & 3) is the scale of pair pc,
+// reads the lane's 12 dwords once per four pairs and lets the MFMA pick
+// the byte: op_sel = pc & 3 on both scale operands, a compile-time
+// constant because the pair loop is unrolled in groups of four. No VALU
+// touches a scale byte.
+//  - sheet layout: dword index row*10 + grp*4 + kgrp (grp = pc >> 2), row
+//    pitch 40 B. ds_read_b32 is served in 32-lane groups with bank =
+//    dword index mod 32 (MI355X_MICROARCH.md, LDS table). A group is the
+//    fragment's 16 rows x two kgrp values (kgrp, kgrp + 1); row*10 mod 32
+//    over 16 consecutive rows is 0,10,20,30,8,18,28,6,16,26,4,14,24,2,12,
+//    22 — the 16 even residues, each once — and the kgrp pair adds 0/1
+//    (or 2/3), so the 32 lanes hit 32 distinct banks: conflict-free. The
+//    fragment base row (multiple of 16) and grp*4 shift all lanes alike.
+//  - staging: glds cannot transpose bytes, so a sheet goes through
+//    registers. Thread t owns half row (row = t & 255, grp = t >> 8, so
+//    grp is wave-uniform): one global_load_dwordx4 of the half row when
+//    rows are whole 16 B pieces (np = 4, 8), else one dword load per
+//    dword that exists (min(4, np - 4*grp), block-uniform branch), each
+//    taken from where v7's staging takes it (scale9_src), 8 v_perm_b32
+//    for the 4x4 byte transpose, two ds_write_b64. Q sheet: once per block, ahead of the
+//    prologue barrier. X sheet: single buffer, written at the tile head
+//    from registers loaded one tile earlier (the first tile's in the
+//    prologue); the load for the next tile is issued right behind the
+//    write, ahead of the tile's first glds, as an ordinary load and is
+//    landed by the interval-0 vmcnt(0) the kernel executes anyway
+//    (writing behind the glds instead measured 1 % slower). The previous tile's trailing barrier has
+//    retired every reader of the old sheet; the interval waits carry
+//    lgkmcnt(0) so the writes are done before the interval-0 barrier.
+//    No new barrier, no new vmcnt wait.
+//    For np not 4 or 8 the per-dword loads make the compiler drain vmcnt
+//    at the tile head; those depths are off the production path.
+//  - pair buffers (pc & 3) and op_sel coincide, so fragment and scale
+//    reads address off two block-lifetime VGPRs each with immediate
+//    offsets.
+//  - counted lgkmcnt per m: with the byte reads gone a pair's read queue
+//    is 12 in-order ds_read_b128 (behind the 12 scale dwords on the first
+//    pair of a group). The four MFMAs of fragment row m start at
+//    lgkmcnt(7 - m) instead of all 32 behind lgkmcnt(0), so Q1-7 land
+//    under the MFMAs of the rows before them (measured -4.2 % on its own,
+//    profiles/README.md).
+// Intervals, barriers, vmcnt(0) placement, pair buffers, fragment reads,
+// MFMA order and the epilogue are v7's: every accumulator sees the same
+// operations in the same order, results are bit-identical.
+// ===========================================================================
+
+#define SCALE9_PITCH 40
+
+typedef uint32_t u32x2_s9 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4_s9 __attribute__((ext_vector_type(4)));
+
+// Where stage_scale_rows (v1..v7) takes sheet byte o of a [rows][sb] scale
+// array from: it stages 16 B pieces and clamps a piece that starts past
+// `last` (the last whole 16 B of the array) onto it. For sb % 16 == 0 that
+// only ever moves rows past the array's end. For other row pitches pieces
+// straddle rows and the clamp also moves the tail of a live last row whose
+// piece sticks out of the array (rows * sb not a multiple of 16). v9 takes
+// every dword from the same place, so the kernels stay interchangeable bit
+// for bit at every shape; changing that rule belongs to all of them at once
+// (docs/NOTES-NEXT.md).
+DEVINL long long scale9_src(long long o, long long last) {
+  long long piece = o & ~15LL;
+  return (piece > last ? last : piece) + (o & 15LL);
+}
+
+// the nd (0..4, wave-uniform) dwords of the half scale row at array byte
+// offset o; w[pl] holds the four kgrp bytes of pair 4*grp + pl, absent
+// pairs read as 0. whole16: sb % 16 == 0, the half row is one 16 B piece.
+DEVINL u32x4_s9 scale9_load(const uint8_t* __restrict__ src, long long o,
+                            long long total, int nd, bool whole16) {
+  long long last = (total >> 4) * 16 - 16;
+  if (last < 0) last = 0;
+  u32x4_s9 w = {0u, 0u, 0u, 0u};
+  if (whole16) {
+    __builtin_memcpy(&w, src + scale9_src(o, last), 16);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (i < nd) {
+        uint32_t t;
+        __builtin_memcpy(&t, src + min(scale9_src(o + 4 * i, last), total - 4), 4);
+        w[i] = t;
+      }
+  }
+  return w;
+}
+
+// 4x4 byte transpose (out[kg] byte pl = w[pl] byte kg) and the two 8 B
+// writes of one half row. v_perm_b32 selector bytes index {b (0..3), a
+// (4..7)} of __builtin_amdgcn_perm(a, b, sel).
+DEVINL void scale9_write(u32x4_s9 w, uint32_t lds_addr) {
+  uint32_t t0 = __builtin_amdgcn_perm(w[1], w[0], 0x05010400u);
+  uint32_t t1 = __builtin_amdgcn_perm(w[1], w[0], 0x07030602u);
+  uint32_t t2 = __builtin_amdgcn_perm(w[3], w[2], 0x05010400u);
+  uint32_t t3 = __builtin_amdgcn_perm(w[3], w[2], 0x07030602u);
+  u32x2_s9 lo, hi;
+  lo[0] = __builtin_amdgcn_perm(t2, t0, 0x05040100u);
+  lo[1] = __builtin_amdgcn_perm(t2, t0, 0x07060302u);
+  hi[0] = __builtin_amdgcn_perm(t3, t1, 0x05040100u);
+  hi[1] = __builtin_amdgcn_perm(t3, t1, 0x07060302u);
+  asm volatile(
+      "ds_write_b64 %0, %1\n\t"
+      "ds_write_b64 %0, %2 offset:8"
+      :: "v"(lds_addr), "v"(lo), "v"(hi) : "memory");
+}
+
+// one pair: pair buffer SEL, op_sel SEL. SCALES: this is the first pair of
+// its 4-pair group and the read blocks also fetch the group's 12 scale
+// dwords (sheet addresses xs_a / qs_a already carry grp*16).
+template <int N>
+DEVINL void fp4v9_wait(bf16x8& q) {
+  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(q) : "n"(N));
+}
+
+template <int SEL, bool SCALES>
+DEVINL void fp4v9_pair(f32x4 (&acc)[8][4], uint32_t xaddr, uint32_t qaddr,
+                       uint32_t xs_a, uint32_t qs_a, uint32_t (&xs_v)[4],
+                       uint32_t (&qs_v)[8]) {
+  constexpr int B = SEL * BM * BK * 2;  // pair buffer SEL, bytes
+  constexpr int SP = 16 * SCALE9_PITCH;  // sheet bytes per 16-row fragment
+  bf16x8 xf[4], qf[8];
+  if constexpr (SCALES) {
+    asm volatile(
+        "ds_read_b32 %4, %9\n\t"
+        "ds_read_b32 %5, %9 offset:%14\n\t"
+        "ds_read_b32 %6, %9 offset:%15\n\t"
+        "ds_read_b32 %7, %9 offset:%16\n\t"
+        "ds_read_b128 %0, %8 offset:%10\n\t"
+        "ds_read_b128 %1, %8 offset:%11\n\t"
+        "ds_read_b128 %2, %8 offset:%12\n\t"
+        "ds_read_b128 %3, %8 offset:%13"
+        : "=&v"(xf[0]), "=&v"(xf[1]), "=&v"(xf[2]), "=&v"(xf[3]),
+          "=&v"(xs_v[0]), "=&v"(xs_v[1]), "=&v"(xs_v[2]), "=&v"(xs_v[3])
+        : "v"(xaddr), "v"(xs_a),
+          "n"(B), "n"(B + 1024), "n"(B + 2048), "n"(B + 3072),
+          "n"(SP), "n"(2 * SP), "n"(3 * SP));
+    asm volatile(
+        "ds_read_b32 %8, %17\n\t"
+        "ds_read_b32 %9, %17 offset:%26\n\t"
+        "ds_read_b32 %10, %17 offset:%27\n\t"
+        "ds_read_b32 %11, %17 offset:%28\n\t"
+        "ds_read_b32 %12, %17 offset:%29\n\t"
+        "ds_read_b32 %13, %17 offset:%30\n\t"
+        "ds_read_b32 %14, %17 offset:%31\n\t"
+        "ds_read_b32 %15, %17 offset:%32\n\t"
+        "ds_read_b128 %0, %16 offset:%18\n\t"
+        "ds_read_b128 %1, %16 offset:%19\n\t"
+        "ds_read_b128 %2, %16 offset:%20\n\t"
+        "ds_read_b128 %3, %16 offset:%21\n\t"
+        "ds_read_b128 %4, %16 offset:%22\n\t"
+        "ds_read_b128 %5, %16 offset:%23\n\t"
+        "ds_read_b128 %6, %16 offset:%24\n\t"
+        "ds_read_b128 %7, %16 offset:%25\n\t"
+        "s_waitcnt lgkmcnt(7)"
+        : "=&v"(qf[0]), "=&v"(qf[1]), "=&v"(qf[2]), "=&v"(qf[3]),
+          "=&v"(qf[4]), "=&v"(qf[5]), "=&v"(qf[6]), "=&v"(qf[7]),
+          "=&v"(qs_v[0]), "=&v"(qs_v[1]), "=&v"(qs_v[2]), "=&v"(qs_v[3]),
+          "=&v"(qs_v[4]), "=&v"(qs_v[5]), "=&v"(qs_v[6]), "=&v"(qs_v[7])
+        : "v"(qaddr), "v"(qs_a),
+          "n"(B), "n"(B + 1024), "n"(B + 2048), "n"(B + 3072),
+          "n"(B + 4096), "n"(B + 5120), "n"(B + 6144), "n"(B + 7168),
+          "n"(SP), "n"(2 * SP), "n"(3 * SP), "n"(4 * SP), "n"(5 * SP),
+          "n"(6 * SP), "n"(7 * SP));
+  } else {
+    asm volatile(
+        "ds_read_b128 %0, %4 offset:%5\n\t"
+        "ds_read_b128 %1, %4 offset:%6\n\t"
+        "ds_read_b128 %2, %4 offset:%7\n\t"
+        "ds_read_b128 %3, %4 offset:%8"
+        : "=&v"(xf[0]), "=&v"(xf[1]), "=&v"(xf[2]), "=&v"(xf[3])
+        : "v"(xaddr),
+          "n"(B), "n"(B + 1024), "n"(B + 2048), "n"(B + 3072));
+    asm volatile(
+        "ds_read_b128 %0, %8 offset:%9\n\t"
+        "ds_read_b128 %1, %8 offset:%10\n\t"
+        "ds_read_b128 %2, %8 offset:%11\n\t"
+        "ds_read_b128 %3, %8 offset:%12\n\t"
+        "ds_read_b128 %4, %8 offset:%13\n\t"
+        "ds_read_b128 %5, %8 offset:%14\n\t"
+        "ds_read_b128 %6, %8 offset:%15\n\t"
+        "ds_read_b128 %7, %8 offset:%16\n\t"
+        "s_waitcnt lgkmcnt(7)"
+        : "=&v"(qf[0]), "=&v"(qf[1]), "=&v"(qf[2]), "=&v"(qf[3]),
+          "=&v"(qf[4]), "=&v"(qf[5]), "=&v"(qf[6]), "=&v"(qf[7])
+        : "v"(qaddr),
+          "n"(B), "n"(B + 1024), "n"(B + 2048), "n"(B + 3072),
+          "n"(B + 4096), "n"(B + 5120), "n"(B + 6144), "n"(B + 7168));
+  }
+  v8i_mx xv[4], qv[8];
+#pragma unroll
+  for (int n = 0; n < 4; ++n) xv[n] = fp4_frag(xf[n]);
+  // the read queue is in order (scale dwords, X0-3, Q0-7) and the Q block
+  // left lgkmcnt(7): all but Q1-7 are in. Group m's MFMAs start once Q_m
+  // is: the wait passes qf[m] through, and the scheduling barrier keeps it
+  // behind group m-1's MFMAs. Group 7's wait is lgkmcnt(0), so a pair
+  // still ends with every one of its LDS reads retired.
+#define FP4V9_GROUP(m)                                                        \
+  {                                                                           \
+    if constexpr ((m) > 0) {                                                  \
+      __builtin_amdgcn_sched_barrier(0);                                      \
+      fp4v9_wait<7 - (m)>(qf[m]);                                             \
+    }                                                                         \
+    qv[m] = fp4_frag(qf[m]);                                                  \
+    _Pragma("unroll") for (int n = 0; n < 4; ++n)                             \
+      acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(           \
+          qv[m], xv[n], acc[m][n], 4 /*A fp4*/, 4 /*B fp4*/,                  \
+          SEL, (int)qs_v[m], SEL, (int)xs_v[n]);                              \
+  }
+  FP4V9_GROUP(0) FP4V9_GROUP(1) FP4V9_GROUP(2) FP4V9_GROUP(3)
+  FP4V9_GROUP(4) FP4V9_GROUP(5) FP4V9_GROUP(6) FP4V9_GROUP(7)
+#undef FP4V9_GROUP
+}
+
+extern "C" __global__ void __launch_bounds__(TK_THREADS)
+topk_scan_fp4_v9_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restrict__ QS,
+                        const uint8_t* __restrict__ X4, const uint8_t* __restrict__ XS,
+                        int nq, int nx, int D, int k, int n_swaths,
+                        float* __restrict__ cand_scores,
+                        int32_t* __restrict__ cand_ids,
+                        const float* __restrict__ theta,
+                        int32_t* __restrict__ tc_n, int cap) {
+  __shared__ bf16 lds_q[4 * BM * BK];
+  __shared__ bf16 lds_x[4 * BN * BK];
+  __shared__ __attribute__((aligned(16))) uint8_t lds_qs[BM * SCALE9_PITCH];
+  __shared__ __attribute__((aligned(16))) uint8_t lds_xs2[BN * SCALE9_PITCH];
+  __shared__ __attribute__((aligned(16))) float row_min[BM];
+#define QP4N(buf) (lds_q + (buf) * BM * BK)
+#define XP4N(buf) (lds_x + (buf) * BN * BK)
+
+  int S = n_swaths;
+  int qb = blockIdx.x / S;
+  int swath = blockIdx.x % S;
+  long long row0 = (long long)qb * BM;
+
+  long long per = ((long long)nx + S - 1) / S;
+  per = ((per + BN - 1) / BN) * BN;
+  long long x_begin = (long long)swath * per;
+  long long x_end = min((long long)nx, x_begin + per);
+  if (x_begin >= x_end) return;
+
+  int wid = wave_id();
+  uint32_t wu = (uint32_t)__builtin_amdgcn_readfirstlane(wid);
+  int wm = wid >> 2, wn = wid & 3;
+  int lane = lane_id();
+  int lrow = lane & 15;
+  int kgrp = lane >> 4;
+  int np = D / (2 * BK_F8);
+  int sb = D / 32;
+  uint32_t ldb = (uint32_t)(D / 2);  // row pitch in bytes
+
+  // scale sheets: this thread's half row (srow, sgrp) and how many of its
+  // four dwords the row really has
+  uint32_t srow = (wu & 3u) * WAVE + (uint32_t)lane;
+  uint32_t sgrp = wu >> 2;
+  int snd = min(4, np - 4 * (int)sgrp);  // <= 0: nothing to stage
+  bool whole16 = (sb & 15) == 0;
+  uint32_t ssheet = srow * SCALE9_PITCH + sgrp * 16u;
+  // the half row of tile row srow of the X sheet tile at xt
+  auto xs_load = [&](long long xt) {
+    return scale9_load(XS, (xt + srow) * (long long)sb + sgrp * 16u,
+                       (long long)nx * sb, snd, whole16);
+  };
+  u32x4_s9 xsr = {0u, 0u, 0u, 0u};
+  if (snd > 0) {
+    u32x4_s9 qsr = scale9_load(QS, (row0 + srow) * (long long)sb + sgrp * 16u,
+                               (long long)nq * sb, snd, whole16);
+    xsr = xs_load(x_begin);
+    scale9_write(qsr, (uint32_t)(size_t)lds_qs + ssheet);
+  }
+
+  for (int i = threadIdx.x; i < BM; i += blockDim.x)
+    row_min[i] = (theta != nullptr && row0 + i < nq) ? theta[row0 + i] : -1e30f;
+  __syncthreads();
+
+  uint32_t qoff[2], xoff[2];
+  const uint8_t* qbase = Q4 + row0 * (long long)ldb;
+  stage_row_offsets(wu, (uint32_t)lane, (uint32_t)min((long long)BM, nq - row0),
+                    ldb, qoff);
+
+  // stage pair s of the Q block and of x tile xt into buffer s & 3
+  auto stage_pair = [&](long long xt, int s) {
+    stage_tile_off(qbase + s * 64, qoff, QP4N(s & 3), wu);
+    stage_tile_off(X4 + xt * (long long)ldb + s * 64, xoff, XP4N(s & 3), wu);
+  };
+  // x tile xt's first interval
+  auto stage_head = [&](long long xt) {
+    stage_row_offsets(wu, (uint32_t)lane, (uint32_t)min((long long)BN, nx - xt),
+                      ldb, xoff);
+    stage_pair(xt, 0);
+    if (np > 1) stage_pair(xt, 1);
+  };
+
+  // block-lifetime read addresses: pair buffer 0 fragments and group 0
+  // scale dwords of the lane's first fragment row
+  uint32_t xrow_base = (uint32_t)(wn * 64 + lrow);
+  uint32_t qrow_base = (uint32_t)(wm * 128 + lrow);
+  uint32_t xaddr = (uint32_t)(size_t)lds_x + lds_off_bytes(xrow_base, (uint32_t)kgrp);
+  uint32_t qaddr = (uint32_t)(size_t)lds_q + lds_off_bytes(qrow_base, (uint32_t)kgrp);
+  uint32_t xs_a0 = (uint32_t)(size_t)lds_xs2 + xrow_base * SCALE9_PITCH
+                   + (uint32_t)kgrp * 4u;
+  uint32_t qs_a0 = (uint32_t)(size_t)lds_qs + qrow_base * SCALE9_PITCH
+                   + (uint32_t)kgrp * 4u;
+
+  for (long long x0 = x_begin; x0 < x_end; x0 += BN) {
+    f32x4 acc[8][4] = {};
+    // this tile's X scale sheet from the registers loaded a tile ago,
+    // then the next tile's half row into the same registers
+    if (snd > 0) {
+      scale9_write(xsr, (uint32_t)(size_t)lds_xs2 + ssheet);
+      if (x0 + BN < x_end) xsr = xs_load(x0 + BN);
+    }
+    stage_head(x0);
+    // pairs in op_sel groups of four; the two 2-pair intervals of a group
+    // are v7's intervals p = 4g and p = 4g + 2
+    for (int g = 0; 4 * g < np; ++g) {
+      int p = 4 * g;
+      uint32_t xs_a = xs_a0 + (uint32_t)g * 16u;
+      uint32_t qs_a = qs_a0 + (uint32_t)g * 16u;
+      uint32_t xs_v[4], qs_v[8];
+      // all outstanding loads are exactly this interval's pairs (plus, at
+      // p == 0, the next tile's X scale half row); lgkmcnt(0) retires the
+      // tile head's sheet writes ahead of the barrier
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      // stage the NEXT interval (pairs p+2, p+3) into the buffers the
+      // PREVIOUS interval consumed; overlaps this interval's compute
+      if (p + 2 < np) stage_pair(x0, p + 2);
+      if (p + 3 < np) stage_pair(x0, p + 3);
+      fp4v9_pair<0, true>(acc, xaddr, qaddr, xs_a, qs_a, xs_v, qs_v);
+      if (p + 1 < np)
+        fp4v9_pair<1, false>(acc, xaddr, qaddr, xs_a, qs_a, xs_v, qs_v);
+      if (p + 2 >= np) break;
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      if (p + 4 < np) stage_pair(x0, p + 4);
+      if (p + 5 < np) stage_pair(x0, p + 5);
+      fp4v9_pair<2, false>(acc, xaddr, qaddr, xs_a, qs_a, xs_v, qs_v);
+      if (p + 3 < np)
+        fp4v9_pair<3, false>(acc, xaddr, qaddr, xs_a, qs_a, xs_v, qs_v);
+    }
+    // nothing is in flight here (the last interval staged nothing); the
+    // barrier orders every wave's last fragment and scale reads (a pair
+    // ends in lgkmcnt(0)) before the next tile's head overwrites buffers
+    // 0,1 and the X scale sheet
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    // the lane's 32 thresholds, th[m][r] = row_min[wm*128 + m*16 +
+    // (lane>>4)*4 + r]
+    f32x4 th[8];
+    {
+      uint32_t ta = (uint32_t)(size_t)row_min
+                    + (uint32_t)(wm * 128 + (lane >> 4) * 4) * 4u;
+      asm volatile(
+          "ds_read_b128 %0, %8\n\t"
+          "ds_read_b128 %1, %8 offset:64\n\t"
+          "ds_read_b128 %2, %8 offset:128\n\t"
+          "ds_read_b128 %3, %8 offset:192\n\t"
+          "ds_read_b128 %4, %8 offset:256\n\t"
+          "ds_read_b128 %5, %8 offset:320\n\t"
+          "ds_read_b128 %6, %8 offset:384\n\t"
+          "ds_read_b128 %7, %8 offset:448\n\t"
+          "s_waitcnt lgkmcnt(0)"
+          : "=&v"(th[0]), "=&v"(th[1]), "=&v"(th[2]), "=&v"(th[3]),
+            "=&v"(th[4]), "=&v"(th[5]), "=&v"(th[6]), "=&v"(th[7])
+          : "v"(ta));
+    }
+    if (k < 0) {
+      if (acc[0][0][0] > 1e29f) cand_scores[0] = acc[0][0][0];
+      continue;
+    }
+    // any-hit test: fmax drops a NaN score exactly as v > theta does
+    bool hit = false;
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float mx = __builtin_fmaxf(
+            __builtin_fmaxf(acc[m][0][r], acc[m][1][r]),
+            __builtin_fmaxf(acc[m][2][r], acc[m][3][r]));
+        hit |= mx > th[m][r];
+      }
+    if (__builtin_amdgcn_ballot_w64(hit) == 0) continue;
+    // slow path, as v7: per-row candidate pointers formed only here
+    int lq = lane >> 4;
+    asm volatile("" : "+v"(lq));
+#pragma unroll
+    for (int m = 0; m < 8; ++m)
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float v = acc[m][n][r];
+          if (!(v > th[m][r])) continue;
+          int row = wm * 128 + m * 16 + lq * 4 + r;
+          long long grow = row0 + row;
+          if (grow >= nq) continue;
+          long long col = x0 + wn * 64 + n * 16 + (lane & 15);
+          if (col >= x_end) continue;
+          int pos = atomicAdd(&tc_n[grow], 1);
+          if (pos < cap) {
+            cand_scores[grow * cap + pos] = v;
+            cand_ids[grow * cap + pos] = int32_t(col);
+          }
+        }
+  }
+}
+
+// ===========================================================================
 // fp4x4 threshold scan v5: v3's 2-pair intervals + tile-resident scales.
 // Q block-scales are invariant across x tiles — staged transposed
 // (SCALE_PITCH sheets) once per BLOCK, read as 8 conflict-free b64 per

@@ -108,7 +108,7 @@ def threshold_bench():
         print(f"{name:24s} {ms:9.2f} ms   {2*nq*rows*dim/1e12/ms*1000:7.1f} TF/s")
 
 
-def fp4_scan_bench(variants=(("v3", 2), ("v7", 7)), iters=5):
+def fp4_scan_bench(variants=(("v3", 2), ("v7", 7), ("v9", 9)), iters=5):
     """fp4x4 threshold scan at 4.2M x 4096 x 1024 with production-like
     theta (tools/ab_fp4v2.py): full vs scan-only (epilogue skipped) per
     kernel variant; the difference is that kernel's epilogue share."""
