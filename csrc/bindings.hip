@@ -81,6 +81,8 @@ __global__ void fact_probe_kernel(const uint8_t*, const int32_t*,
 __global__ void fp4_quantize_append_kernel(const uint16_t*, const int32_t*, int, long long,
                                            int, long long, uint16_t*, uint8_t*, uint8_t*,
                                            int32_t*, const int32_t*, float*, float);
+__global__ void index_move_rows_kernel(const int32_t*, const int32_t*, long long, int, int,
+                                       uint4*, uint4*, uint32_t*, uint32_t*, uint32_t*);
 struct AuditRecord64;
 __global__ void audit_pack_kernel(const int8_t*, const float*, const unsigned long long*,
                                   const unsigned long long*, const int32_t*, const float*,
@@ -692,6 +694,81 @@ void index_append(torch::Tensor feats, c10::optional<torch::Tensor> src_idx,
                              osp, sdp, (float)salience_init);
 }
 
+// -- forgetting: in-place row moves (csrc/index_forget.hip) ----------------
+
+void index_move_rows(torch::Tensor src, torch::Tensor dst,
+                     c10::optional<torch::Tensor> index,
+                     c10::optional<torch::Tensor> X4, c10::optional<torch::Tensor> XS,
+                     c10::optional<torch::Tensor> owner,
+                     c10::optional<torch::Tensor> salience) {
+  // row dst[j] of every given buffer <- row src[j], bitwise, in one launch;
+  // a pair with an index outside [0, cap) is skipped by the kernel
+  CHECK_GPU(src); CHECK_CONTIG(src); CHECK_GPU(dst); CHECK_CONTIG(dst);
+  TORCH_CHECK(src.dtype() == torch::kInt32 && dst.dtype() == torch::kInt32 &&
+              src.dim() == 1 && dst.dim() == 1, "src/dst must be int32 [m]");
+  TORCH_CHECK(src.numel() == dst.numel(), "src and dst differ in length");
+  TORCH_CHECK(src.device() == dst.device(), "src and dst on different devices");
+  TORCH_CHECK(index.has_value() || X4.has_value() || owner.has_value() ||
+              salience.has_value(), "index_move_rows needs at least one buffer");
+  TORCH_CHECK(X4.has_value() == XS.has_value(), "X4 and XS go together");
+  long long cap = -1;
+  int D = 0;
+  auto same_cap = [&](const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.device() == src.device(), name, " and src on different devices");
+    if (cap < 0) cap = t.size(0);
+    TORCH_CHECK(t.size(0) == cap, name, " differs in capacity from the other buffers");
+  };
+  uint4* ip = nullptr;
+  if (index.has_value()) {
+    CHECK_GPU((*index)); CHECK_CONTIG((*index));
+    TORCH_CHECK(index->dtype() == torch::kBFloat16 && index->dim() == 2,
+                "index must be bf16 [cap, D]");
+    D = index->size(1);
+    TORCH_CHECK(D > 0 && D % 8 == 0, "index rows must be a multiple of 16 bytes (D%8==0)");
+    TORCH_CHECK(aligned16(*index), "index must be 16-byte aligned");
+    same_cap(*index, "index");
+    ip = reinterpret_cast<uint4*>(index->data_ptr());
+  }
+  uint4* x4p = nullptr; uint32_t* xsp = nullptr;
+  if (X4.has_value()) {
+    TORCH_CHECK(X4->dim() == 2, "X4 must be [cap, D/2]");
+    int D4 = (int)X4->size(1) * 2;
+    TORCH_CHECK(!index.has_value() || D4 == D, "index and X4 differ in D");
+    D = D4;
+    TORCH_CHECK(D > 0 && D % 128 == 0 && D <= 2048, "fp4 rows need D%128==0, D<=2048");
+    check_fp4_dst(*X4, *XS, X4->size(0), D);
+    same_cap(*X4, "X4");
+    same_cap(*XS, "XS");
+    x4p = reinterpret_cast<uint4*>(X4->data_ptr());
+    xsp = reinterpret_cast<uint32_t*>(XS->data_ptr());
+  }
+  uint32_t* op = nullptr;
+  if (owner.has_value()) {
+    CHECK_GPU((*owner)); CHECK_CONTIG((*owner));
+    TORCH_CHECK(owner->dtype() == torch::kInt32 && owner->dim() == 1, "owner must be int32 [cap]");
+    same_cap(*owner, "owner");
+    op = reinterpret_cast<uint32_t*>(owner->data_ptr());
+  }
+  uint32_t* sp = nullptr;
+  if (salience.has_value()) {
+    CHECK_GPU((*salience)); CHECK_CONTIG((*salience));
+    TORCH_CHECK(salience->dtype() == torch::kFloat32 && salience->dim() == 1,
+                "salience must be f32 [cap]");
+    same_cap(*salience, "salience");
+    sp = reinterpret_cast<uint32_t*>(salience->data_ptr());
+  }
+  TORCH_CHECK(cap < (1LL << 31), "index has too many rows");
+  long long m = src.numel();
+  if (m == 0) return;
+  // one wave per pair, 4 waves per block; memory-bound: cap the grid and
+  // stride the rest
+  long long blocks = (m + 3) / 4;
+  if (blocks > 256 * 8) blocks = 256 * 8;
+  hipLaunchKernelGGL(index_move_rows_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                     cur_stream(), src.data_ptr<int32_t>(), dst.data_ptr<int32_t>(), m,
+                     (int)cap, D, ip, x4p, xsp, op, sp);
+}
+
 void register_host_envelope(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -802,6 +879,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("X4") = c10::nullopt, py::arg("XS") = c10::nullopt,
         py::arg("owner_dst") = c10::nullopt, py::arg("owner_src") = c10::nullopt,
         py::arg("salience_dst") = c10::nullopt, py::arg("salience_init") = 1.0);
+  m.def("index_move_rows", &index_move_rows,
+        "move rows src[j] onto rows dst[j] of the live recall index buffers, in place",
+        py::arg("src"), py::arg("dst"), py::arg("index") = c10::nullopt,
+        py::arg("X4") = c10::nullopt, py::arg("XS") = c10::nullopt,
+        py::arg("owner") = c10::nullopt, py::arg("salience") = c10::nullopt);
   m.def("edit_distance", [](torch::Tensor bytes, torch::Tensor offsets) {
     // batched Levenshtein over string PAIRS: offsets has 2*n+1 entries;
     // pair i = strings (2i, 2i+1) in the packed byte buffer

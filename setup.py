@@ -22,6 +22,7 @@ SOURCES = [
     "csrc/gemm_nt.hip",
     "csrc/topk_recall.hip",
     "csrc/fp4_quantize.hip",
+    "csrc/index_forget.hip",
     "csrc/firewall.hip",
     "csrc/edit_distance.hip",
     "csrc/fact_probe.hip",

@@ -19,6 +19,16 @@
              ingested rows) and random-letter messages (no clusters). Also
              prints per-stage hipEvent ms and how many queries per step took
              the direct-kernel fallback of the threshold recall.
+  forget     forgetting at the index shape (--index x --dim, 50M x 1024):
+             1 % of the rows evicted from a salience vector with realistic
+             ties. evict_mask and forget_plan ms; the move kernel
+             (csrc/index_forget.hip) ms and GB/s, bytes = read + written,
+             against the same plan executed with torch indexing on the same
+             buffers, alternating the two; then the pipeline with
+             ingest_full="evict" driven past a full shard: the evicting
+             step's ms against the median plain step, per kind of content
+             (--content). Results live in profiles/README.md, section
+             "index forget".
 
 Every mode needs a GPU and prints one JSON line per measurement.
 """
@@ -26,6 +36,7 @@ Every mode needs a GPU and prints one JSON line per measurement.
 import argparse
 import gc
 import json
+import math
 import os
 import sys
 import time
@@ -107,17 +118,21 @@ def mode_append(args):
                       "GBps_median": round(nbytes / t["ms_median"] / 1e6, 1)}), flush=True)
 
 
+def random_batch(n, seed):
+    """Random-letter messages: content without clusters."""
+    from vainplex_openclaw_amd.pipeline.synth import TOOL_RISKS, SynthBatch
+
+    rng = np.random.default_rng(seed)
+    msgs = [rng.integers(97, 123, size=300, dtype=np.uint8).tobytes() for _ in range(n)]
+    return SynthBatch(msgs, rng.integers(0, 64, size=n).astype(np.int32),
+                      rng.choice(TOOL_RISKS, size=n).astype(np.float32),
+                      np.zeros(n, dtype=np.int8))
+
+
 def mode_ingest(args):
     from vainplex_openclaw_amd.pipeline.engine import (
         V_DENY, FirewallPipeline, PipelineConfig, StagingRing)
-    from vainplex_openclaw_amd.pipeline.synth import TOOL_RISKS, SynthBatch, synthetic_batch
-
-    def random_batch(n, seed):
-        rng = np.random.default_rng(seed)
-        msgs = [rng.integers(97, 123, size=300, dtype=np.uint8).tobytes() for _ in range(n)]
-        return SynthBatch(msgs, rng.integers(0, 64, size=n).astype(np.int32),
-                          rng.choice(TOOL_RISKS, size=n).astype(np.float32),
-                          np.zeros(n, dtype=np.int8))
+    from vainplex_openclaw_amd.pipeline.synth import synthetic_batch
 
     # queries that overflow or underflow the threshold scan's candidate
     # buffer are redone by the direct kernel: count them
@@ -173,10 +188,131 @@ def mode_ingest(args):
         torch.cuda.empty_cache()
 
 
+def _realistic_salience(n, batch_rows=3750, seed=3):
+    """A salience vector with the ties a long-running shard has: rows
+    ingested in one step and never recalled share a value bit for bit
+    (0.9999^age, floored at 0.01, so the oldest 40 % sit on the floor), and
+    2 % of the rows were recalled at some time and carry values of their
+    own."""
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    steps = (n + batch_rows - 1) // batch_rows
+    # the oldest step first; age chosen so that 40 % of the steps are floored
+    age = torch.arange(steps, 0, -1, device="cuda", dtype=torch.float64)
+    age = age * (math.log(0.01) / math.log(0.9999) / (0.6 * steps))
+    per_step = (0.9999 ** age).clamp_min(0.01).float()
+    sal = per_step.repeat_interleave(batch_rows)[:n].contiguous()
+    hit = torch.rand(n, generator=gen, device="cuda") < 0.02
+    own = torch.rand(n, generator=gen, device="cuda")
+    return torch.where(hit, sal + 0.25 * own * (1.0 - sal), sal)
+
+
+def mode_forget(args):
+    from vainplex_openclaw_amd.pipeline.engine import (
+        FirewallPipeline, PipelineConfig, StagingRing)
+    from vainplex_openclaw_amd.pipeline.synth import synthetic_batch
+
+    D = args.dim
+    n = (args.index // 128) * 128
+    count = n // 100
+    index = torch.empty(n, D, dtype=torch.bfloat16, device="cuda")
+    x4 = torch.empty(n, D // 2, dtype=torch.uint8, device="cuda")
+    xs = torch.empty(n, D // 32, dtype=torch.uint8, device="cuda")
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    for buf in (index.view(torch.int16), x4.view(torch.int16), xs.view(torch.int16)):
+        for i in range(0, n, 1_000_000):
+            c = buf[i:i + 1_000_000]
+            c.copy_(torch.randint(-32768, 32768, c.shape, generator=gen,
+                                  dtype=torch.int16, device="cuda"))
+    owner = torch.arange(n, dtype=torch.int32, device="cuda")
+    sal = _realistic_salience(n)
+    uniq = int(torch.unique(sal).numel())
+    common = {"mode": "forget", "rows": n, "D": D, "evict": count}
+
+    def emit(op, t, **kw):
+        print(json.dumps({**common, "op": op, **{k: round(v, 4) for k, v in t.items()}, **kw}),
+              flush=True)
+
+    dead = g.evict_mask(sal, count)
+    assert int(dead.sum()) == count
+    emit("evict_mask", _time(lambda: g.evict_mask(sal, count), 5, warmup=1),
+         distinct_saliences=uniq)
+    n_new, dst, src = g.forget_plan(dead)
+    emit("forget_plan", _time(lambda: g.forget_plan(dead), 5, warmup=1),
+         n_new=n_new, moved=int(dst.numel()))
+
+    # the move is idempotent (sources stay, destinations are rewritten with
+    # the same bytes), so the kernel and the baseline run the same plan
+    # again and again on the same buffers: no second copy of the index
+    m = int(dst.numel())
+    row_bytes = 2 * D + D // 2 + D // 32 + 4 + 4
+    nbytes = 2 * m * row_bytes  # read + written
+    bufs = dict(index=index, X4=x4, XS=xs, owner=owner, salience=sal)
+
+    def by_indexing():
+        s, d = src.long(), dst.long()
+        for b in bufs.values():
+            b[d] = b[s]
+
+    res = {}
+    for rnd in range(2):
+        for name, fn in (("index_move_rows", lambda: g.index_move_rows(src, dst, **bufs)),
+                         ("torch_indexing", by_indexing)):
+            res.setdefault(name, []).append(_time(fn, 5, warmup=1))
+    probe = torch.arange(0, m, max(1, m // 4096), device="cuda")
+    same = all(bool(torch.equal(b[dst[probe].long()].view(torch.uint8),
+                                b[src[probe].long()].view(torch.uint8)))
+               for b in bufs.values())
+    for name, runs in res.items():
+        for rnd, t in enumerate(runs):
+            emit(name, t, round=rnd, moved=m, bytes=nbytes, rows_match=same,
+                 GBps_median=round(nbytes / t["ms_median"] / 1e6, 1))
+    del index, x4, xs, owner, sal, dead, dst, src, bufs, probe
+    gc.collect()
+    torch.cuda.empty_cache()
+
+    # the pipeline driven past a full shard: one evicting step against the
+    # plain steps around it (host clock, a synchronize after every step)
+    make = {"synthetic": lambda i: synthetic_batch(args.batch, seed=i),
+            "random": lambda i: random_batch(args.batch, i)}
+    total = args.steps + args.warmup
+    for content, rnd in ((c, r) for c in args.content.split(",") for r in range(args.rounds)):
+        pool = [make[content](i) for i in range(4)]
+        cfg = PipelineConfig(batch=args.batch, dim=D, index_size=n, ingest=True,
+                             ingest_capacity=(args.warmup + 2) * args.batch,
+                             ingest_full="evict")
+        pipe = FirewallPipeline(cfg, device="cuda:0")
+        ring = StagingRing(pipe, max_bytes=8 << 20, max_msgs=max(args.batch, 8192) + 1)
+        plain, evicting = [], []
+        for i in range(total):
+            staged = ring.stage(pool[i % len(pool)])
+            epoch = pipe.forget_epoch
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pipe.step(None, staged=staged)
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1000
+            if pipe.forget_epoch != epoch:
+                evicting.append(round(ms, 3))
+            elif i >= args.warmup:
+                plain.append(ms)
+        plain.sort()
+        print(json.dumps({"mode": "forget", "op": "ingest_evict", "content": content,
+                          "round": rnd,
+                          "index_rows": n, "capacity": pipe.capacity, "batch": args.batch,
+                          "evict_frac": cfg.evict_frac, "forgotten": pipe.forgotten,
+                          "dropped": pipe.ingest_dropped, "rows_after": pipe.n_rows,
+                          "plain_step_ms_median": round(plain[len(plain) // 2], 3),
+                          "plain_steps": len(plain), "evicting_step_ms": evicting}),
+              flush=True)
+        del pipe, ring, staged
+        gc.collect()
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("mode", choices=["quantize", "append", "ingest"])
+    ap.add_argument("mode", choices=["quantize", "append", "ingest", "forget"])
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--dim", type=int, default=1024)
     ap.add_argument("--index", type=int, default=50_000_000)
@@ -184,11 +320,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--content", default="synthetic,random",
-                    help="ingest mode: comma list of synthetic, random")
+                    help="ingest and forget modes: comma list of synthetic, random")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
-    {"quantize": mode_quantize, "append": mode_append, "ingest": mode_ingest}[args.mode](args)
+    {"quantize": mode_quantize, "append": mode_append, "ingest": mode_ingest,
+     "forget": mode_forget}[args.mode](args)
 
 
 if __name__ == "__main__":

@@ -139,8 +139,12 @@ class MembraneEngine:
         return "\n".join(lines)
 
     def decay_pass(self, agent: str) -> int:
-        """Periodic maintenance: prune fully-decayed memories."""
-        return self.store.prune(agent)
+        """Periodic maintenance: prune fully-decayed memories from the
+        store and their rows from the index. Returns the count."""
+        self.flush_buffer()  # every stored record has its row by now
+        victims = self.store.prune(agent, return_ids=True)
+        self.index.remove(victims)
+        return len(victims)
 
     def flush(self) -> None:
         self.flush_buffer()

@@ -111,6 +111,34 @@ class SalienceIndex:
         self.owners.extend([agent] * n)
         self.size += n
 
+    def remove(self, record_ids: Sequence[str]) -> int:
+        """Forget the rows of `record_ids` (unknown ids are ignored) and
+        compact in place by ops.gpu.forget_plan: survivors from the tail
+        move into the holes, so row order is not preserved. Returns the
+        number of rows removed."""
+        gone = set(record_ids)
+        dead = np.fromiter((rid in gone for rid in self.ids), dtype=bool, count=self.size)
+        if not dead.any():
+            return 0
+        from ..ops import gpu as g
+
+        n_new, dst, src = g.forget_plan(torch.from_numpy(dead))
+        if self.use_gpu:
+            g.index_move_rows(src.to(self.device), dst.to(self.device),
+                              index=self._mat, owner=self._owner)
+        else:
+            d, s = dst.numpy(), src.numpy()
+            self._mat_np[d] = self._mat_np[s]
+            self._owner_np[d] = self._owner_np[s]
+        for d, s in zip(dst.tolist(), src.tolist()):
+            self.ids[d] = self.ids[s]
+            self.owners[d] = self.owners[s]
+        del self.ids[n_new:]
+        del self.owners[n_new:]
+        removed = self.size - n_new
+        self.size = n_new
+        return removed
+
     # -- search ------------------------------------------------------------
     def search(self, agent: str, query: str, k: int) -> List[Tuple[str, float]]:
         """Top-k (record_id, cosine) for ONE agent. The matrix is shared

@@ -133,9 +133,11 @@ class MemoryStore:
         rec["recalls"] = rec.get("recalls", 0) + 1
         self._savers[agent].mark_dirty()
 
-    def prune(self, agent: str, min_salience: float = MIN_SALIENCE * 2, max_records: int = 0) -> int:
+    def prune(self, agent: str, min_salience: float = MIN_SALIENCE * 2, max_records: int = 0,
+              return_ids: bool = False):
         """Drop fully-decayed records; optionally cap the store size
-        (lowest effective salience evicted first)."""
+        (lowest effective salience evicted first). Returns the count, or
+        with return_ids the list of dropped record ids (for the index)."""
         m = self._agent_map(agent)
         now = self._clock()
         victims = [rid for rid, r in m.items() if self.decayed_salience(r, now) <= min_salience]
@@ -148,7 +150,7 @@ class MemoryStore:
                 victims.append(r["id"])
         if victims:
             self._savers[agent].mark_dirty()
-        return len(victims)
+        return victims if return_ids else len(victims)
 
     def flush(self) -> None:
         for agent, saver in self._savers.items():

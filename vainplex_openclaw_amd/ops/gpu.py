@@ -395,6 +395,97 @@ def index_append(
                        owner_dst, owner_src, salience_dst, float(salience_init))
 
 
+def evict_mask(salience: torch.Tensor, count: int) -> torch.Tensor:
+    """bool[n] marking exactly min(max(count, 0), n) rows of `salience`
+    (fp32 [n]), the lowest ones. Deterministic: with v the count-th
+    smallest value every row with s < v is marked, and among the rows with
+    s == v the lowest row indices until the count is reached. Ties are the
+    normal case (rows ingested in one step and never recalled share a value
+    bit for bit, and so do all rows at the floor). Pure torch, no host
+    read; runs on CPU tensors too."""
+    n = salience.numel()
+    c = min(max(int(count), 0), n)
+    if c == 0:
+        return torch.zeros(n, dtype=torch.bool, device=salience.device)
+    if c == n:
+        return torch.ones(n, dtype=torch.bool, device=salience.device)
+    v = torch.topk(salience, c, largest=False, sorted=False).values.max()
+    below = salience < v
+    tie = salience == v
+    room = c - below.sum()
+    # 1-based rank of a tie among the ties, by row index
+    rank = torch.cumsum(tie, dim=0, dtype=torch.int32)
+    return below | (tie & (rank <= room))
+
+
+def forget_plan(dead: torch.Tensor) -> Tuple[int, torch.Tensor, torch.Tensor]:
+    """The compaction rule of forgetting (hole filling). `dead` is bool[n]
+    over the live rows; with n_new = n - dead.sum(), dst is the dead rows
+    below n_new and src the live rows at or above n_new, both ascending
+    int32 and equally long. Moving row src[j] onto row dst[j] for every j
+    makes [:n_new] the live rows. Sources and destinations are disjoint and
+    the destinations unique, so the moves need no order. At most
+    min(#dead, n_new) rows move.
+
+    Row order is NOT preserved: a survivor from the tail lands in a hole.
+    Nothing depends on row order; salience carries age.
+
+    n_new is the one value read back to the host (the two nonzero() calls
+    size their outputs from the same mask)."""
+    n = dead.numel()
+    n_new = n - int(dead.sum())
+    dst = torch.nonzero(dead[:n_new]).flatten().to(torch.int32)
+    src = (torch.nonzero(~dead[n_new:]).flatten() + n_new).to(torch.int32)
+    return n_new, dst, src
+
+
+def index_move_rows(
+    src: torch.Tensor,
+    dst: torch.Tensor,
+    index: Optional[torch.Tensor] = None,
+    X4: Optional[torch.Tensor] = None,
+    XS: Optional[torch.Tensor] = None,
+    owner: Optional[torch.Tensor] = None,
+    salience: Optional[torch.Tensor] = None,
+) -> None:
+    """Row dst[j] of every given buffer takes the contents of row src[j],
+    bitwise and in place, in one launch (csrc/index_forget.hip). `index`
+    is bf16 [cap, D], X4/XS the MXFP4 pair, owner int32 [cap], salience
+    fp32 [cap]; any subset, at least one. dst must be unique and disjoint
+    from src (forget_plan's lists are). The kernel skips a pair with an
+    index outside [0, cap). CPU tensors, and a bf16 row that is not a
+    multiple of 16 bytes (D % 8 != 0), take torch indexing instead."""
+    bufs = [b for b in (index, X4, XS, owner, salience) if b is not None]
+    if not bufs:
+        raise ValueError("index_move_rows needs at least one buffer")
+    if src.numel() == 0:
+        return
+    on_gpu = src.is_cuda and all(b.is_cuda for b in bufs)
+    if on_gpu and (index is None or index.shape[1] % 8 == 0):
+        ext().index_move_rows(src, dst, index, X4, XS, owner, salience)
+        return
+    s, d = src.long(), dst.long()
+    for b in bufs:
+        b[d] = b[s]
+
+
+def index_forget(
+    dead: torch.Tensor,
+    index: Optional[torch.Tensor] = None,
+    X4: Optional[torch.Tensor] = None,
+    XS: Optional[torch.Tensor] = None,
+    owner: Optional[torch.Tensor] = None,
+    salience: Optional[torch.Tensor] = None,
+) -> int:
+    """Forget the live rows marked in `dead` (bool[n], n = live rows):
+    forget_plan, then one index_move_rows over the given buffers. Returns
+    n_new; the live rows are then [:n_new] of every buffer and the
+    contents of rows >= n_new are unspecified."""
+    n_new, dst, src = forget_plan(dead)
+    index_move_rows(src, dst, index=index, X4=X4, XS=XS, owner=owner, salience=salience)
+    return n_new
+
+
 def topk_recall_fp8(Q8: torch.Tensor, X8: torch.Tensor, k: int, n_swaths: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """Stage-1 fp8 scan: candidate ids ranked by e4m3 cosine (csrc
     topk_recall_fp8_kernel). Inputs are uint8 views of e4m3 bytes."""

@@ -25,7 +25,9 @@ messages:
      (csrc/sha256_merkle.hip)
   8. (cfg.ingest) Membrane ingest (csrc/fp4_quantize.hip): the messages
      that were not denied are appended to the live index shard — bf16 row,
-     MXFP4 codes + scales, owner, salience — and later steps recall them
+     MXFP4 codes + scales, owner, salience — and later steps recall them;
+     with ingest_full="evict" a full shard first forgets its lowest-
+     salience rows and is compacted in place (csrc/index_forget.hip)
 
 Multi-GPU (one process per GPU, torch.distributed over RCCL/xGMI):
 the index is sharded across ranks; recall queries are all-gathered so
@@ -38,6 +40,7 @@ rows.
 
 from __future__ import annotations
 
+import math
 import threading
 import time
 from dataclasses import dataclass
@@ -98,10 +101,17 @@ class PipelineConfig:
     recall_isolation: bool = False
     # online memory ingest: every step appends its non-denied messages to
     # the recall index (csrc/fp4_quantize.hip, one launch) so later steps
-    # recall them; ingest_capacity = spare rows per shard, append-only,
-    # messages past a full index are counted in ingest_dropped
+    # recall them; ingest_capacity = spare rows per shard; what happens at
+    # a full index is ingest_full's choice
     ingest: bool = False
     ingest_capacity: int = 0
+    # what ingest does when the kept messages do not fit the free rows:
+    # "drop" counts them in ingest_dropped; "evict" first forgets the
+    # lowest-salience live rows (FirewallPipeline.forget), at least
+    # evict_frac of the capacity at a time so that the selection is paid
+    # once in many steps. Ignored without ingest.
+    ingest_full: str = "drop"
+    evict_frac: float = 0.01
 
 
 class StageProfiler:
@@ -176,6 +186,12 @@ class FirewallPipeline:
             self.n_rows = cfg.index_size
             self.capacity = cfg.index_size + (max(0, cfg.ingest_capacity) if cfg.ingest else 0)
             self.ingest_dropped = 0
+            if cfg.ingest and cfg.ingest_full not in ("drop", "evict"):
+                raise ValueError(f"ingest_full must be 'drop' or 'evict', not {cfg.ingest_full!r}")
+            # rows forgotten so far, and the number of forgets that moved
+            # rows: recall_ids from before a forget name rows as they were
+            self.forgotten = 0
+            self.forget_epoch = 0
             cap = self.capacity
             self.index = torch.empty(cap, cfg.dim, dtype=torch.bfloat16, device=self.device)
             self.index[cfg.index_size:].zero_()
@@ -292,15 +308,74 @@ class FirewallPipeline:
         self.is_hot = torch.zeros(self.capacity, dtype=torch.bool, device=self.device)
         self.is_hot[self.hot_idx] = True
 
+    def forget(self, count: Optional[int] = None,
+               min_salience: Optional[float] = None) -> int:
+        """Forget live rows of this rank's shard and compact the index in
+        place. Exactly one argument is given: `count` forgets the `count`
+        lowest-salience live rows (g.evict_mask: ties go by row index);
+        `min_salience` forgets every live row with salience <=
+        min_salience (the store's prune rule; operators would pass 0.02).
+        Returns the number of rows forgotten.
+
+        Index, fp4 copy, owners and salience are compacted by one
+        g.index_forget (hole filling, csrc/index_forget.hip): survivors
+        from the tail move into the holes, so row order is not preserved
+        and row ids change. recall_ids returned by earlier steps name rows
+        as of their step and are stale once forget_epoch has moved on. The
+        contents of rows [n_rows, capacity) are unspecified afterwards;
+        nothing reads them. Rank-local: no collective, global ids keep the
+        capacity stride."""
+        if (count is None) == (min_salience is None):
+            raise ValueError("forget: give exactly one of count and min_salience")
+        if self.index8 is not None:
+            raise ValueError("forget: no move path for the e4m3 index copy")
+        n = self.n_rows
+        sal = self.salience[:n]
+        if count is not None:
+            dead = g.evict_mask(sal, count)
+        else:
+            dead = sal <= float(min_salience)
+        gone = None
+        if self.owner_counts is not None:
+            # taken before the move: afterwards the rows hold other owners
+            A = self.owner_counts.numel()
+            own = self.index_owner[:n].long()
+            gone = torch.bincount(torch.where(dead, own, torch.full_like(own, A)),
+                                  minlength=A + 1)[:A]
+        x4, xs = self.index4 if self.index4 is not None else (None, None)
+        n_new = g.index_forget(dead, index=self.index, X4=x4, XS=xs,
+                               owner=self.index_owner, salience=self.salience)
+        removed = n - n_new
+        if removed == 0:
+            return 0
+        self.n_rows = n_new
+        if gone is not None:
+            self.owner_counts -= gone
+        if self.cfg.recall_mode == "threshold_banded":
+            # hot_idx, hot_X and is_hot hold row ids from before the move
+            self._refresh_hot_band()
+        self.forgotten += removed
+        self.forget_epoch += 1
+        return removed
+
     def _ingest(self, feats: torch.Tensor, verdict: torch.Tensor,
                 agent_idx: torch.Tensor) -> None:
         """Remember this step's messages: append every feature row whose
         verdict is not deny to the live index (bf16 row, fp4 codes and
         scales, owner, salience 1.0) with one g.index_append launch. The
         nonzero() is the step's one host read (the kept count). Append
-        only: rows that do not fit are counted in ingest_dropped."""
+        only with ingest_full="drop": rows that do not fit are counted in
+        ingest_dropped. With "evict" the lowest-salience live rows are
+        forgotten first, max(missing rows, evict_frac * capacity) of them;
+        the step's recall and salience update are done by then, so its own
+        results do not change, and only a step that keeps more messages
+        than the whole capacity still drops the excess."""
         src = torch.nonzero(verdict != V_DENY).flatten().to(torch.int32)
         kept = int(src.numel())
+        free = self.capacity - self.n_rows
+        if self.cfg.ingest_full == "evict" and kept > free:
+            batch = math.ceil(self.cfg.evict_frac * self.capacity)
+            self.forget(count=min(max(kept - free, batch), self.n_rows))
         take = min(kept, self.capacity - self.n_rows)
         self.ingest_dropped += kept - take
         if take == 0:
