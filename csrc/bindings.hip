@@ -55,6 +55,9 @@ __global__ void topk_scan_fp4_v7_kernel(const uint8_t*, const uint8_t*, const ui
 __global__ void topk_scan_fp4_v9_kernel(const uint8_t*, const uint8_t*, const uint8_t*,
                                         const uint8_t*, int, int, int, int, int,
                                         float*, int32_t*, const float*, int32_t*, int);
+__global__ void topk_scan_fp4_v10_kernel(const uint8_t*, const uint8_t*, const uint8_t*,
+                                         const uint8_t*, int, int, int, int, int,
+                                         float*, int32_t*, const float*, int32_t*, int);
 __global__ void topk_scan_fp4_owned_kernel(const uint8_t*, const uint8_t*, const uint8_t*,
                                            const uint8_t*, int, int, int, int, int,
                                            float*, int32_t*, const float*, int32_t*, int,
@@ -424,8 +427,8 @@ static std::vector<torch::Tensor> fp4x4_scan(
     bool scan_only, const torch::Tensor* xowner, const torch::Tensor* qowner) {
   // both operands MXFP4 (csrc topk_scan_fp4_kernel); scores at x1.
   // variant_arg: -1 = environment/default, 0 = v1, 1 = v2, 2 = v3,
-  // 4 = v5, 7 = v7, 9 = v9. scan_only runs the K-loops without the epilogue
-  // (k = -1) for epilogue-share attribution.
+  // 4 = v5, 7 = v7, 9 = v9, 10 = v10. scan_only runs the K-loops without
+  // the epilogue (k = -1) for epilogue-share attribution.
   CHECK_GPU(Q4); CHECK_CONTIG(Q4); CHECK_GPU(QS); CHECK_CONTIG(QS);
   CHECK_GPU(X4); CHECK_CONTIG(X4); CHECK_GPU(XS); CHECK_CONTIG(XS);
   CHECK_GPU(theta); CHECK_CONTIG(theta);
@@ -436,21 +439,24 @@ static std::vector<torch::Tensor> fp4x4_scan(
   TORCH_CHECK(X4.size(1) == D / 2 && XS.size(0) == nx && XS.size(1) == D / 32);
   TORCH_CHECK(theta.numel() == nq && cap >= 32 && cap <= 4096);
   if (xowner != nullptr) check_owners(*xowner, *qowner, nx, nq);
-  // v9 (v7 + transposed scale sheets read as one dword per fragment per
-  // four pairs with the byte picked by op_sel, counted lgkmcnt per m) is
-  // the default: bit-exact vs v1 and measured 9.7 vs 11.0 ms at 4.2M x
-  // 4096. Env overrides for A/B; VAINPLEX_FP4_V7=1 is the way back to v7.
+  // v10 (v9 = v7 + transposed scale sheets read as one dword per fragment
+  // per four pairs with the byte picked by op_sel, counted lgkmcnt per m;
+  // v10 = v9 on the fragment swizzle that is conflict-free on the real
+  // ds_read_b128 lane groups) is the default: bit-exact vs v1, and every
+  // bench run below every v9 run, 109.7 vs 114.8 ms/step (profiles/README).
+  // Env overrides for A/B; VAINPLEX_FP4_V9=1 is the way back to v9.
   static const int env_variant = [] {
     if (const char* e = getenv("VAINPLEX_FP4_V1"); e && e[0] == '1') return 0;
     if (const char* e = getenv("VAINPLEX_FP4_V2"); e && e[0] == '1') return 1;
     if (const char* e = getenv("VAINPLEX_FP4_V3"); e && e[0] == '1') return 2;
     if (const char* e = getenv("VAINPLEX_FP4_V5"); e && e[0] == '1') return 4;
     if (const char* e = getenv("VAINPLEX_FP4_V7"); e && e[0] == '1') return 7;
-    return 9;
+    if (const char* e = getenv("VAINPLEX_FP4_V9"); e && e[0] == '1') return 9;
+    return 10;
   }();
   int variant = variant_arg < 0 ? env_variant : (int)variant_arg;
   TORCH_CHECK(variant == 0 || variant == 1 || variant == 2 || variant == 4 ||
-              variant == 7 || variant == 9,
+              variant == 7 || variant == 9 || variant == 10,
               "fp4x4 scan: unknown variant ", variant);
   int n_qblocks = (nq + 255) / 256;
   if (n_swaths <= 0) {
@@ -476,7 +482,8 @@ static std::vector<torch::Tensor> fp4x4_scan(
                        qowner->data_ptr<int32_t>());
     return {cand_s, cand_i, counts};
   }
-  auto kern = variant == 9 ? topk_scan_fp4_v9_kernel
+  auto kern = variant == 10 ? topk_scan_fp4_v10_kernel
+            : variant == 9 ? topk_scan_fp4_v9_kernel
             : variant == 7 ? topk_scan_fp4_v7_kernel
             : variant == 4 ? topk_scan_fp4_v5_kernel
             : variant == 2 ? topk_scan_fp4_v3_kernel

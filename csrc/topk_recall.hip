@@ -43,10 +43,28 @@
 #define AS3 __attribute__((address_space(3)))
 
 // LDS tile addressing: row-major [rows][BK] bf16, 64 B per row = 4 slots
-// of 16 B. Swizzle: slot' = slot ^ ((row>>2)&3) -> each 16-lane
-// ds_read_b128 group covers 16 distinct bank-quads: conflict-free.
+// of 16 B. Swizzle: slot' = slot ^ ((row>>2)&3). That would be
+// conflict-free if ds_read_b128 were served in groups of 16 contiguous
+// lanes. The real groups are {0-3,12-15,20-27}, {4-11,16-19,28-31} and the
+// same +32 (common.hpp, kDsReadB128Groups): in each of them this XOR puts
+// two row quads on the same sixteen banks, a 2-way conflict on every
+// fragment read (static_assert in common.hpp). Kept for v1..v9 and the
+// bf16/fp8/mx kernels, which are A/B baselines off the bench path.
 DEVINL uint32_t lds_off_bytes(uint32_t row, uint32_t slot) {
-  return (row * 4u + (slot ^ ((row >> 2u) & 3u))) * 16u;
+  return (row * 4u + frag_swz_slot_contig(row, slot)) * 16u;
+}
+
+// The same image with the swizzle that is conflict-free on the real lane
+// groups (frag_swz_slot, proven in common.hpp). SWZ selects the slot
+// function: 0 = the contiguous-group XOR above, 1 = group-aware.
+template <int SWZ>
+DEVINL uint32_t swz_slot(uint32_t row, uint32_t slot) {
+  if constexpr (SWZ) return frag_swz_slot(row, slot);
+  else return frag_swz_slot_contig(row, slot);
+}
+template <int SWZ>
+DEVINL uint32_t lds_off_bytes_swz(uint32_t row, uint32_t slot) {
+  return (row * 4u + swz_slot<SWZ>(row, slot)) * 16u;
 }
 
 // Stage a [rows x BK] tile into LDS via global_load_lds. Destination is
@@ -1730,6 +1748,22 @@ DEVINL void stage_row_offsets(uint32_t w, uint32_t lane, uint32_t rows_live,
   }
 }
 
+// the same offsets with the source slot picked by swz_slot<SWZ>, the
+// staging side of lds_off_bytes_swz<SWZ>. A lane's four-lane set still
+// reads one whole 64 B row segment: coalescing does not depend on SWZ.
+template <int SWZ>
+DEVINL void stage_row_offsets_swz(uint32_t w, uint32_t lane, uint32_t rows_live,
+                                  uint32_t ld_bytes, uint32_t off[2]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    uint32_t piece = w * WAVE + i * TK_THREADS + lane;
+    uint32_t r = piece >> 2;
+    uint32_t src_slot = swz_slot<SWZ>(r, piece & 3);
+    if (r >= rows_live) r = rows_live - 1;
+    off[i] = r * ld_bytes + src_slot * 16u;
+  }
+}
+
 // stage one pair tile: base is wave-uniform (tile row0 * ld + pair * 64)
 DEVINL void stage_tile_off(const uint8_t* __restrict__ base,
                            const uint32_t off[2], bf16* lds_base, uint32_t w) {
@@ -2168,19 +2202,46 @@ DEVINL void fp4v9_pair(f32x4 (&acc)[8][4], uint32_t xaddr, uint32_t qaddr,
 #undef FP4V9_GROUP
 }
 
-extern "C" __global__ void __launch_bounds__(TK_THREADS)
-topk_scan_fp4_v9_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restrict__ QS,
-                        const uint8_t* __restrict__ X4, const uint8_t* __restrict__ XS,
-                        int nq, int nx, int D, int k, int n_swaths,
-                        float* __restrict__ cand_scores,
-                        int32_t* __restrict__ cand_ids,
-                        const float* __restrict__ theta,
-                        int32_t* __restrict__ tc_n, int cap) {
+// ---------------------------------------------------------------------------
+// v10: v9 on the group-aware fragment swizzle. v9's image uses slot ^
+// ((row>>2)&3), conflict-free on contiguous 16-lane groups; on the real
+// ds_read_b128 groups every fragment read is 2-way conflicted (8 LDS cycles
+// instead of 4; SQ_LDS_BANK_CONFLICT residue of 12 reads x 4 cycles per
+// wave-pair). v10 takes the slot from frag_swz_slot (common.hpp, proven
+// there by static_assert) on both sides: the staging source slot
+// (stage_row_offsets_swz) and the read address (lds_off_bytes_swz). The XOR
+// term still depends on the row through (row>>2)&3 only, so the
+// block-lifetime read addresses with immediate offsets survive, the glds
+// destination stays lane-linear, and every accumulator sees the same
+// operands in the same order: bit-identical to v9 and v1.
+//
+// One body serves three kernels, which differ in nothing else:
+//   topk_scan_fp4_v9_kernel     SWZ = 0, unfiltered
+//   topk_scan_fp4_v10_kernel    SWZ = 1, unfiltered
+//   topk_scan_fp4_owned_kernel  SWZ = 1, owner-filtered (prologue, row-owner
+//                               loads and two-gate epilogue described at
+//                               the kernel)
+// ---------------------------------------------------------------------------
+
+typedef int32_t i32x4_own __attribute__((ext_vector_type(4)));
+
+template <int SWZ, bool OWNED>
+DEVINL void fp4_scan_body(const uint8_t* __restrict__ Q4, const uint8_t* __restrict__ QS,
+                          const uint8_t* __restrict__ X4, const uint8_t* __restrict__ XS,
+                          int nq, int nx, int D, int k, int n_swaths,
+                          float* __restrict__ cand_scores,
+                          int32_t* __restrict__ cand_ids,
+                          const float* __restrict__ theta,
+                          int32_t* __restrict__ tc_n, int cap,
+                          const int32_t* __restrict__ xowner,
+                          const int32_t* __restrict__ qowner) {
   __shared__ bf16 lds_q[4 * BM * BK];
   __shared__ bf16 lds_x[4 * BN * BK];
   __shared__ __attribute__((aligned(16))) uint8_t lds_qs[BM * SCALE9_PITCH];
   __shared__ __attribute__((aligned(16))) uint8_t lds_xs2[BN * SCALE9_PITCH];
   __shared__ __attribute__((aligned(16))) float row_min[BM];
+  // owner filter only: query owners, -1 = unfiltered, -2 = garbage row
+  __shared__ __attribute__((aligned(16))) int32_t row_owner[OWNED ? BM : 4];
 #define QP4N(buf) (lds_q + (buf) * BM * BK)
 #define XP4N(buf) (lds_x + (buf) * BN * BK)
 
@@ -2225,14 +2286,26 @@ topk_scan_fp4_v9_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
     scale9_write(qsr, (uint32_t)(size_t)lds_qs + ssheet);
   }
 
-  for (int i = threadIdx.x; i < BM; i += blockDim.x)
-    row_min[i] = (theta != nullptr && row0 + i < nq) ? theta[row0 + i] : -1e30f;
+  for (int i = threadIdx.x; i < BM; i += blockDim.x) {
+    bool live = row0 + i < nq;
+    row_min[i] = (theta != nullptr && live) ? theta[row0 + i] : -1e30f;
+    if constexpr (OWNED) {
+      int32_t qo = live ? qowner[row0 + i] : -2;
+      row_owner[i] = (live && qo < 0) ? -1 : qo;
+    }
+  }
   __syncthreads();
+
+  // owner filter: does any of this wave's 128 query rows see every row?
+  bool wave_wild = false;
+  if constexpr (OWNED)
+    wave_wild = __builtin_amdgcn_ballot_w64(
+        row_owner[wm * 128 + lane] == -1 || row_owner[wm * 128 + 64 + lane] == -1) != 0;
 
   uint32_t qoff[2], xoff[2];
   const uint8_t* qbase = Q4 + row0 * (long long)ldb;
-  stage_row_offsets(wu, (uint32_t)lane, (uint32_t)min((long long)BM, nq - row0),
-                    ldb, qoff);
+  stage_row_offsets_swz<SWZ>(wu, (uint32_t)lane,
+                             (uint32_t)min((long long)BM, nq - row0), ldb, qoff);
 
   // stage pair s of the Q block and of x tile xt into buffer s & 3
   auto stage_pair = [&](long long xt, int s) {
@@ -2241,8 +2314,8 @@ topk_scan_fp4_v9_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
   };
   // x tile xt's first interval
   auto stage_head = [&](long long xt) {
-    stage_row_offsets(wu, (uint32_t)lane, (uint32_t)min((long long)BN, nx - xt),
-                      ldb, xoff);
+    stage_row_offsets_swz<SWZ>(wu, (uint32_t)lane,
+                               (uint32_t)min((long long)BN, nx - xt), ldb, xoff);
     stage_pair(xt, 0);
     if (np > 1) stage_pair(xt, 1);
   };
@@ -2251,8 +2324,10 @@ topk_scan_fp4_v9_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
   // scale dwords of the lane's first fragment row
   uint32_t xrow_base = (uint32_t)(wn * 64 + lrow);
   uint32_t qrow_base = (uint32_t)(wm * 128 + lrow);
-  uint32_t xaddr = (uint32_t)(size_t)lds_x + lds_off_bytes(xrow_base, (uint32_t)kgrp);
-  uint32_t qaddr = (uint32_t)(size_t)lds_q + lds_off_bytes(qrow_base, (uint32_t)kgrp);
+  uint32_t xaddr = (uint32_t)(size_t)lds_x
+                   + lds_off_bytes_swz<SWZ>(xrow_base, (uint32_t)kgrp);
+  uint32_t qaddr = (uint32_t)(size_t)lds_q
+                   + lds_off_bytes_swz<SWZ>(qrow_base, (uint32_t)kgrp);
   uint32_t xs_a0 = (uint32_t)(size_t)lds_xs2 + xrow_base * SCALE9_PITCH
                    + (uint32_t)kgrp * 4u;
   uint32_t qs_a0 = (uint32_t)(size_t)lds_qs + qrow_base * SCALE9_PITCH
@@ -2260,6 +2335,17 @@ topk_scan_fp4_v9_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
 
   for (long long x0 = x_begin; x0 < x_end; x0 += BN) {
     f32x4 acc[8][4] = {};
+    // owner filter: the lane's 4 row owners (columns n*16 + lrow); they fly
+    // under the K-loop, landed by the interval-0 vmcnt(0). Columns past
+    // x_end carry -3: matches nothing, not even an unfiltered query.
+    int32_t xo[4] = {-3, -3, -3, -3};
+    if constexpr (OWNED) {
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        long long col = x0 + wn * 64 + n * 16 + lrow;
+        if (col < x_end) xo[n] = xowner[col];
+      }
+    }
     // this tile's X scale sheet from the registers loaded a tile ago,
     // then the next tile's half row into the same registers
     if (snd > 0) {
@@ -2338,6 +2424,43 @@ topk_scan_fp4_v9_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
         hit |= mx > th[m][r];
       }
     if (__builtin_amdgcn_ballot_w64(hit) == 0) continue;
+    // owner filter: the lane's 32 query owners, qo[m][r] laid out like
+    // th[m][r], read only behind the score gate
+    i32x4_own qo[8];
+    if constexpr (OWNED) {
+      uint32_t oa = (uint32_t)(size_t)row_owner
+                    + (uint32_t)(wm * 128 + (lane >> 4) * 4) * 4u;
+      asm volatile(
+          "ds_read_b128 %0, %8\n\t"
+          "ds_read_b128 %1, %8 offset:64\n\t"
+          "ds_read_b128 %2, %8 offset:128\n\t"
+          "ds_read_b128 %3, %8 offset:192\n\t"
+          "ds_read_b128 %4, %8 offset:256\n\t"
+          "ds_read_b128 %5, %8 offset:320\n\t"
+          "ds_read_b128 %6, %8 offset:384\n\t"
+          "ds_read_b128 %7, %8 offset:448\n\t"
+          "s_waitcnt lgkmcnt(0)"
+          : "=&v"(qo[0]), "=&v"(qo[1]), "=&v"(qo[2]), "=&v"(qo[3]),
+            "=&v"(qo[4]), "=&v"(qo[5]), "=&v"(qo[6]), "=&v"(qo[7])
+          : "v"(oa));
+      // gate 2: any (score > theta && owner match) in the wave. Scores of
+      // foreign columns are replaced by -inf, then the test is gate 1's.
+      if (!wave_wild) {
+        bool hit2 = false;
+#pragma unroll
+        for (int m = 0; m < 8; ++m)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float mx = -__builtin_inff();
+#pragma unroll
+            for (int n = 0; n < 4; ++n)
+              mx = __builtin_fmaxf(mx, qo[m][r] == xo[n] ? acc[m][n][r]
+                                                        : -__builtin_inff());
+            hit2 |= mx > th[m][r];
+          }
+        if (__builtin_amdgcn_ballot_w64(hit2) == 0) continue;
+      }
+    }
     // slow path, as v7: per-row candidate pointers formed only here
     int lq = lane >> 4;
     asm volatile("" : "+v"(lq));
@@ -2349,6 +2472,8 @@ topk_scan_fp4_v9_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
         for (int r = 0; r < 4; ++r) {
           float v = acc[m][n][r];
           if (!(v > th[m][r])) continue;
+          if constexpr (OWNED)
+            if (!(qo[m][r] == xo[n] || qo[m][r] == -1)) continue;
           int row = wm * 128 + m * 16 + lq * 4 + r;
           long long grow = row0 + row;
           if (grow >= nq) continue;
@@ -2361,6 +2486,32 @@ topk_scan_fp4_v9_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
           }
         }
   }
+#undef QP4N
+#undef XP4N
+}
+
+extern "C" __global__ void __launch_bounds__(TK_THREADS)
+topk_scan_fp4_v9_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restrict__ QS,
+                        const uint8_t* __restrict__ X4, const uint8_t* __restrict__ XS,
+                        int nq, int nx, int D, int k, int n_swaths,
+                        float* __restrict__ cand_scores,
+                        int32_t* __restrict__ cand_ids,
+                        const float* __restrict__ theta,
+                        int32_t* __restrict__ tc_n, int cap) {
+  fp4_scan_body<0, false>(Q4, QS, X4, XS, nq, nx, D, k, n_swaths, cand_scores,
+                          cand_ids, theta, tc_n, cap, nullptr, nullptr);
+}
+
+extern "C" __global__ void __launch_bounds__(TK_THREADS)
+topk_scan_fp4_v10_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restrict__ QS,
+                         const uint8_t* __restrict__ X4, const uint8_t* __restrict__ XS,
+                         int nq, int nx, int D, int k, int n_swaths,
+                         float* __restrict__ cand_scores,
+                         int32_t* __restrict__ cand_ids,
+                         const float* __restrict__ theta,
+                         int32_t* __restrict__ tc_n, int cap) {
+  fp4_scan_body<1, false>(Q4, QS, X4, XS, nq, nx, D, k, n_swaths, cand_scores,
+                          cand_ids, theta, tc_n, cap, nullptr, nullptr);
 }
 
 // ===========================================================================
@@ -2539,9 +2690,11 @@ topk_scan_fp4_v5_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
 
 
 // ===========================================================================
-// fp4x4 threshold scan, owner-filtered (agent-isolated recall): v7's tile
-// geometry, LDS image, K-loop, staging and candidate-append format with an
-// owner-aware epilogue. A (query, row) pair is eligible iff the query is
+// fp4x4 threshold scan, owner-filtered (agent-isolated recall): the v10
+// scan (fp4_scan_body: transposed scale sheets, op_sel, counted waits,
+// group-aware fragment swizzle) with an owner-aware prologue and epilogue;
+// tile geometry, staging and candidate-append format are the unfiltered
+// kernel's. A (query, row) pair is eligible iff the query is
 // unfiltered (qowner < 0) or xowner[row] == qowner[query].
 //  - query owners: staged once per block into LDS (1 KB), -1 = unfiltered,
 //    -2 = garbage row (grow >= nq, matches nothing). Read like the
@@ -2560,8 +2713,6 @@ topk_scan_fp4_v5_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
 //    exact either way.
 // ===========================================================================
 
-typedef int32_t i32x4_own __attribute__((ext_vector_type(4)));
-
 extern "C" __global__ void __launch_bounds__(TK_THREADS)
 topk_scan_fp4_owned_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restrict__ QS,
                            const uint8_t* __restrict__ X4, const uint8_t* __restrict__ XS,
@@ -2572,246 +2723,7 @@ topk_scan_fp4_owned_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __rest
                            int32_t* __restrict__ tc_n, int cap,
                            const int32_t* __restrict__ xowner,
                            const int32_t* __restrict__ qowner) {
-  __shared__ bf16 lds_q[4 * BM * BK];
-  __shared__ bf16 lds_x[4 * BN * BK];
-  __shared__ uint8_t lds_qs[BM * 32];
-  __shared__ uint8_t lds_xs2[BN * 32];
-  __shared__ __attribute__((aligned(16))) float row_min[BM];
-  __shared__ __attribute__((aligned(16))) int32_t row_owner[BM];
-#define QP4O(buf) (lds_q + (buf) * BM * BK)
-#define XP4O(buf) (lds_x + (buf) * BN * BK)
-
-  int S = n_swaths;
-  int qb = blockIdx.x / S;
-  int swath = blockIdx.x % S;
-  long long row0 = (long long)qb * BM;
-
-  long long per = ((long long)nx + S - 1) / S;
-  per = ((per + BN - 1) / BN) * BN;
-  long long x_begin = (long long)swath * per;
-  long long x_end = min((long long)nx, x_begin + per);
-  if (x_begin >= x_end) return;
-
-  for (int i = threadIdx.x; i < BM; i += blockDim.x) {
-    bool live = row0 + i < nq;
-    row_min[i] = (theta != nullptr && live) ? theta[row0 + i] : -1e30f;
-    int32_t qo = live ? qowner[row0 + i] : -2;
-    row_owner[i] = (live && qo < 0) ? -1 : qo;
-  }
-  __syncthreads();
-
-  int wid = wave_id();
-  uint32_t wu = (uint32_t)__builtin_amdgcn_readfirstlane(wid);
-  int wm = wid >> 2, wn = wid & 3;
-  int lane = lane_id();
-  int lrow = lane & 15;
-  int kgrp = lane >> 4;
-  int np = D / (2 * BK_F8);
-  int sb = D / 32;
-  uint32_t ldb = (uint32_t)(D / 2);  // row pitch in bytes
-
-  // does any of this wave's 128 query rows see every row?
-  bool wave_wild = __builtin_amdgcn_ballot_w64(
-      row_owner[wm * 128 + lane] == -1 || row_owner[wm * 128 + 64 + lane] == -1) != 0;
-
-  uint32_t qoff[2], xoff[2];
-  const uint8_t* qbase = Q4 + row0 * (long long)ldb;
-  stage_row_offsets(wu, (uint32_t)lane, (uint32_t)min((long long)BM, nq - row0),
-                    ldb, qoff);
-
-  auto stage_pair = [&](long long xt, int s) {
-    stage_tile_off(qbase + s * 64, qoff, QP4O(s & 3), wu);
-    stage_tile_off(X4 + xt * (long long)ldb + s * 64, xoff, XP4O(s & 3), wu);
-  };
-  auto stage_head = [&](long long xt) {
-    stage_row_offsets(wu, (uint32_t)lane, (uint32_t)min((long long)BN, nx - xt),
-                      ldb, xoff);
-    stage_scale_rows(XS, sb, xt, (long long)nx, lds_xs2, BN);
-    stage_pair(xt, 0);
-    if (np > 1) stage_pair(xt, 1);
-  };
-
-  stage_scale_rows(QS, sb, row0, (long long)nq, lds_qs, BM);
-
-  for (long long x0 = x_begin; x0 < x_end; x0 += BN) {
-    f32x4 acc[8][4] = {};
-    // the lane's 4 row owners; they fly under the K-loop
-    int32_t xo[4];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      long long col = x0 + wn * 64 + n * 16 + lrow;
-      xo[n] = col < x_end ? xowner[col] : -3;
-    }
-    stage_head(x0);
-    for (int p = 0; p < np; p += 2) {
-      int pe = min(p + 2, np);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (p + 2 < np) stage_pair(x0, p + 2);
-      if (p + 3 < np) stage_pair(x0, p + 3);
-      for (int pc = p; pc < pe; ++pc) {
-        uint32_t xrow_base = (uint32_t)(wn * 64 + lrow);
-        uint32_t qrow_base = (uint32_t)(wm * 128 + lrow);
-        uint32_t xaddr = (uint32_t)(size_t)XP4O(pc & 3)
-                         + lds_off_bytes(xrow_base, (uint32_t)kgrp);
-        uint32_t qaddr = (uint32_t)(size_t)QP4O(pc & 3)
-                         + lds_off_bytes(qrow_base, (uint32_t)kgrp);
-        uint32_t sst = 16u * (uint32_t)sb;
-        uint32_t xs_a = (uint32_t)(size_t)lds_xs2 + xrow_base * (uint32_t)sb
-                        + (uint32_t)(pc * 4 + kgrp);
-        uint32_t qs_a = (uint32_t)(size_t)lds_qs + qrow_base * (uint32_t)sb
-                        + (uint32_t)(pc * 4 + kgrp);
-        bf16x8 xf[4], qf[8];
-        uint32_t xs_v[4], qs_v[8];
-        asm volatile(
-            "ds_read_b128 %0, %8\n\t"
-            "ds_read_b128 %1, %8 offset:1024\n\t"
-            "ds_read_b128 %2, %8 offset:2048\n\t"
-            "ds_read_b128 %3, %8 offset:3072\n\t"
-            "ds_read_u8 %4, %9\n\t"
-            "ds_read_u8 %5, %10\n\t"
-            "ds_read_u8 %6, %11\n\t"
-            "ds_read_u8 %7, %12\n\t"
-            "s_waitcnt lgkmcnt(0)"
-            : "=&v"(xf[0]), "=&v"(xf[1]), "=&v"(xf[2]), "=&v"(xf[3]),
-              "=&v"(xs_v[0]), "=&v"(xs_v[1]), "=&v"(xs_v[2]), "=&v"(xs_v[3])
-            : "v"(xaddr), "v"(xs_a), "v"(xs_a + sst), "v"(xs_a + 2 * sst),
-              "v"(xs_a + 3 * sst));
-        asm volatile(
-            "ds_read_b128 %0, %16\n\t"
-            "ds_read_b128 %1, %16 offset:1024\n\t"
-            "ds_read_b128 %2, %16 offset:2048\n\t"
-            "ds_read_b128 %3, %16 offset:3072\n\t"
-            "ds_read_b128 %4, %16 offset:4096\n\t"
-            "ds_read_b128 %5, %16 offset:5120\n\t"
-            "ds_read_b128 %6, %16 offset:6144\n\t"
-            "ds_read_b128 %7, %16 offset:7168\n\t"
-            "ds_read_u8 %8, %17\n\t"
-            "ds_read_u8 %9, %18\n\t"
-            "ds_read_u8 %10, %19\n\t"
-            "ds_read_u8 %11, %20\n\t"
-            "ds_read_u8 %12, %21\n\t"
-            "ds_read_u8 %13, %22\n\t"
-            "ds_read_u8 %14, %23\n\t"
-            "ds_read_u8 %15, %24\n\t"
-            "s_waitcnt lgkmcnt(0)"
-            : "=&v"(qf[0]), "=&v"(qf[1]), "=&v"(qf[2]), "=&v"(qf[3]),
-              "=&v"(qf[4]), "=&v"(qf[5]), "=&v"(qf[6]), "=&v"(qf[7]),
-              "=&v"(qs_v[0]), "=&v"(qs_v[1]), "=&v"(qs_v[2]), "=&v"(qs_v[3]),
-              "=&v"(qs_v[4]), "=&v"(qs_v[5]), "=&v"(qs_v[6]), "=&v"(qs_v[7])
-            : "v"(qaddr), "v"(qs_a), "v"(qs_a + sst), "v"(qs_a + 2 * sst),
-              "v"(qs_a + 3 * sst), "v"(qs_a + 4 * sst), "v"(qs_a + 5 * sst),
-              "v"(qs_a + 6 * sst), "v"(qs_a + 7 * sst));
-        v8i_mx xv[4], qv[8];
-#pragma unroll
-        for (int n = 0; n < 4; ++n) xv[n] = fp4_frag(xf[n]);
-#pragma unroll
-        for (int m = 0; m < 8; ++m) qv[m] = fp4_frag(qf[m]);
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-#pragma unroll
-          for (int n = 0; n < 4; ++n)
-            acc[m][n] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-                qv[m], xv[n], acc[m][n], 4 /*A fp4*/, 4 /*B fp4*/,
-                0, (int)qs_v[m], 0, (int)xs_v[n]);
-      }
-    }
-    // as in v7: nothing in flight; the barrier orders every wave's last
-    // fragment reads before the next tile's head restages buffers 0,1
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    f32x4 th[8];
-    {
-      uint32_t ta = (uint32_t)(size_t)row_min
-                    + (uint32_t)(wm * 128 + (lane >> 4) * 4) * 4u;
-      asm volatile(
-          "ds_read_b128 %0, %8\n\t"
-          "ds_read_b128 %1, %8 offset:64\n\t"
-          "ds_read_b128 %2, %8 offset:128\n\t"
-          "ds_read_b128 %3, %8 offset:192\n\t"
-          "ds_read_b128 %4, %8 offset:256\n\t"
-          "ds_read_b128 %5, %8 offset:320\n\t"
-          "ds_read_b128 %6, %8 offset:384\n\t"
-          "ds_read_b128 %7, %8 offset:448\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(th[0]), "=&v"(th[1]), "=&v"(th[2]), "=&v"(th[3]),
-            "=&v"(th[4]), "=&v"(th[5]), "=&v"(th[6]), "=&v"(th[7])
-          : "v"(ta));
-    }
-    if (k < 0) {
-      if (acc[0][0][0] > 1e29f) cand_scores[0] = acc[0][0][0];
-      continue;
-    }
-    // gate 1 (v7's): score-only any-hit
-    bool hit = false;
-#pragma unroll
-    for (int m = 0; m < 8; ++m)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float mx = __builtin_fmaxf(
-            __builtin_fmaxf(acc[m][0][r], acc[m][1][r]),
-            __builtin_fmaxf(acc[m][2][r], acc[m][3][r]));
-        hit |= mx > th[m][r];
-      }
-    if (__builtin_amdgcn_ballot_w64(hit) == 0) continue;
-    // the lane's 32 query owners, qo[m][r] laid out like th[m][r]
-    i32x4_own qo[8];
-    {
-      uint32_t oa = (uint32_t)(size_t)row_owner
-                    + (uint32_t)(wm * 128 + (lane >> 4) * 4) * 4u;
-      asm volatile(
-          "ds_read_b128 %0, %8\n\t"
-          "ds_read_b128 %1, %8 offset:64\n\t"
-          "ds_read_b128 %2, %8 offset:128\n\t"
-          "ds_read_b128 %3, %8 offset:192\n\t"
-          "ds_read_b128 %4, %8 offset:256\n\t"
-          "ds_read_b128 %5, %8 offset:320\n\t"
-          "ds_read_b128 %6, %8 offset:384\n\t"
-          "ds_read_b128 %7, %8 offset:448\n\t"
-          "s_waitcnt lgkmcnt(0)"
-          : "=&v"(qo[0]), "=&v"(qo[1]), "=&v"(qo[2]), "=&v"(qo[3]),
-            "=&v"(qo[4]), "=&v"(qo[5]), "=&v"(qo[6]), "=&v"(qo[7])
-          : "v"(oa));
-    }
-    // gate 2: any (score > theta && owner match) in the wave. Scores of
-    // foreign columns are replaced by -inf, then the test is gate 1's.
-    if (!wave_wild) {
-      bool hit2 = false;
-#pragma unroll
-      for (int m = 0; m < 8; ++m)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float mx = -__builtin_inff();
-#pragma unroll
-          for (int n = 0; n < 4; ++n)
-            mx = __builtin_fmaxf(mx, qo[m][r] == xo[n] ? acc[m][n][r]
-                                                      : -__builtin_inff());
-          hit2 |= mx > th[m][r];
-        }
-      if (__builtin_amdgcn_ballot_w64(hit2) == 0) continue;
-    }
-    int lq = lane >> 4;
-    asm volatile("" : "+v"(lq));
-#pragma unroll
-    for (int m = 0; m < 8; ++m)
-#pragma unroll
-      for (int n = 0; n < 4; ++n)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float v = acc[m][n][r];
-          bool eligible = qo[m][r] == xo[n] || qo[m][r] == -1;
-          if (!(v > th[m][r] && eligible)) continue;
-          int row = wm * 128 + m * 16 + lq * 4 + r;
-          long long grow = row0 + row;
-          if (grow >= nq) continue;
-          long long col = x0 + wn * 64 + n * 16 + (lane & 15);
-          if (col >= x_end) continue;
-          int pos = atomicAdd(&tc_n[grow], 1);
-          if (pos < cap) {
-            cand_scores[grow * cap + pos] = v;
-            cand_ids[grow * cap + pos] = int32_t(col);
-          }
-        }
-  }
+  fp4_scan_body<1, true>(Q4, QS, X4, XS, nq, nx, D, k, n_swaths, cand_scores,
+                         cand_ids, theta, tc_n, cap, xowner, qowner);
 }
+

@@ -108,7 +108,7 @@ def threshold_bench():
         print(f"{name:24s} {ms:9.2f} ms   {2*nq*rows*dim/1e12/ms*1000:7.1f} TF/s")
 
 
-def fp4_scan_bench(variants=(("v3", 2), ("v7", 7), ("v9", 9)), iters=5):
+def fp4_scan_bench(variants=(("v7", 7), ("v9", 9), ("v10", 10)), iters=5):
     """fp4x4 threshold scan at 4.2M x 4096 x 1024 with production-like
     theta (tools/ab_fp4v2.py): full vs scan-only (epilogue skipped) per
     kernel variant; the difference is that kernel's epilogue share."""
@@ -156,8 +156,9 @@ def timed_median(fn, iters=9, warmup=3):
 
 def fp4_owned_scan_bench(n_owners, iters=9):
     """Cost of the in-kernel owner filter at the fp4_scan_bench shape, one
-    session: v7 and v3 unfiltered (the yardsticks), then the owned kernel
-    with 1 owner (same candidates as v7) and with `n_owners` uniform random
+    session: v9 and v10 unfiltered (the yardsticks; the owned kernel shares
+    v10's K-loop), then the owned kernel with 1 owner (same candidates as
+    the unfiltered scans) and with `n_owners` uniform random
     owners. Thresholds are per owner (ops.gpu.owned_thresholds) with the
     candidate target that makes the 1-owner theta the unfiltered bench's
     mu + 4.2 sigma, so every config expects the same candidates per query."""
@@ -186,10 +187,10 @@ def fp4_owned_scan_bench(n_owners, iters=9):
 
     theta = (mu + 4.2 * sigma).contiguous()
     configs = [
-        ("v7 unfiltered", lambda: g.ext().topk_scan_threshold_fp4x4(
-            Q4, QS, X4, XS, theta, cap, 0, 7, False)),
-        ("v3 unfiltered", lambda: g.ext().topk_scan_threshold_fp4x4(
-            Q4, QS, X4, XS, theta, cap, 0, 2, False)),
+        ("v9 unfiltered", lambda: g.ext().topk_scan_threshold_fp4x4(
+            Q4, QS, X4, XS, theta, cap, 0, 9, False)),
+        ("v10 unfiltered", lambda: g.ext().topk_scan_threshold_fp4x4(
+            Q4, QS, X4, XS, theta, cap, 0, 10, False)),
         ("owned, 1 owner", owned(1)),
     ]
     if n_owners > 1:
