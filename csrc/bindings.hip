@@ -62,6 +62,16 @@ __global__ void topk_scan_fp4_owned_kernel(const uint8_t*, const uint8_t*, const
                                            const uint8_t*, int, int, int, int, int,
                                            float*, int32_t*, const float*, int32_t*, int,
                                            const int32_t*, const int32_t*);
+__global__ void topk_scan_fp4_hist_kernel(const uint8_t*, const uint8_t*, const uint8_t*,
+                                          const uint8_t*, int, int, int, int, int,
+                                          float*, int32_t*, const float*, int32_t*, int,
+                                          int32_t*, const float*, const float*);
+__global__ void topk_scan_fp4_owned_hist_kernel(const uint8_t*, const uint8_t*,
+                                                const uint8_t*, const uint8_t*, int, int,
+                                                int, int, int, float*, int32_t*,
+                                                const float*, int32_t*, int,
+                                                const int32_t*, const int32_t*,
+                                                int32_t*, const float*, const float*);
 
 __global__ void topk_merge_kernel(const float*, const int32_t*, int, int, int,
                                   float*, int32_t*);
@@ -424,7 +434,8 @@ torch::Tensor audit_pack(torch::Tensor verdict, torch::Tensor risk, torch::Tenso
 static std::vector<torch::Tensor> fp4x4_scan(
     torch::Tensor Q4, torch::Tensor QS, torch::Tensor X4, torch::Tensor XS,
     torch::Tensor theta, int64_t cap, int64_t n_swaths, int64_t variant_arg,
-    bool scan_only, const torch::Tensor* xowner, const torch::Tensor* qowner) {
+    bool scan_only, const torch::Tensor* xowner, const torch::Tensor* qowner,
+    const torch::Tensor* hist_w = nullptr) {
   // both operands MXFP4 (csrc topk_scan_fp4_kernel); scores at x1.
   // variant_arg: -1 = environment/default, 0 = v1, 1 = v2, 2 = v3,
   // 4 = v5, 7 = v7, 9 = v9, 10 = v10. scan_only runs the K-loops without
@@ -471,6 +482,39 @@ static std::vector<torch::Tensor> fp4x4_scan(
   auto cand_i = torch::full({(long long)nq, cap}, -1, i32opts);
   auto counts = torch::zeros({(long long)nq}, i32opts);
   dim3 grid((unsigned)(n_qblocks * n_swaths));
+  if (hist_w != nullptr) {
+    // v10 / owned scan that also counts, by score bin, the hits that found
+    // the buffer full: bins of width hist_w[q] above theta[q] (csrc
+    // topk_scan_fp4_hist_kernel, ops.gpu.hist_bin_spec)
+    const torch::Tensor& w = *hist_w;
+    CHECK_GPU(w); CHECK_CONTIG(w);
+    TORCH_CHECK(theta.dtype() == torch::kFloat32 && w.dtype() == torch::kFloat32,
+                "theta and w must be float32");
+    TORCH_CHECK(w.dim() == 1 && w.numel() == nq, "w must have one entry per query");
+    auto inv_w = w.reciprocal();
+    auto hist = torch::zeros({(long long)nq, 256}, i32opts);
+    if (xowner != nullptr)
+      hipLaunchKernelGGL(topk_scan_fp4_owned_hist_kernel, grid, dim3(512), 0,
+                         cur_stream(),
+                         Q4.data_ptr<uint8_t>(), QS.data_ptr<uint8_t>(),
+                         X4.data_ptr<uint8_t>(), XS.data_ptr<uint8_t>(),
+                         nq, (int)nx, D, 1, (int)n_swaths,
+                         cand_s.data_ptr<float>(), cand_i.data_ptr<int32_t>(),
+                         theta.data_ptr<float>(), counts.data_ptr<int32_t>(),
+                         (int)cap, xowner->data_ptr<int32_t>(),
+                         qowner->data_ptr<int32_t>(), hist.data_ptr<int32_t>(),
+                         w.data_ptr<float>(), inv_w.data_ptr<float>());
+    else
+      hipLaunchKernelGGL(topk_scan_fp4_hist_kernel, grid, dim3(512), 0, cur_stream(),
+                         Q4.data_ptr<uint8_t>(), QS.data_ptr<uint8_t>(),
+                         X4.data_ptr<uint8_t>(), XS.data_ptr<uint8_t>(),
+                         nq, (int)nx, D, 1, (int)n_swaths,
+                         cand_s.data_ptr<float>(), cand_i.data_ptr<int32_t>(),
+                         theta.data_ptr<float>(), counts.data_ptr<int32_t>(),
+                         (int)cap, hist.data_ptr<int32_t>(),
+                         w.data_ptr<float>(), inv_w.data_ptr<float>());
+    return {cand_s, cand_i, counts, hist};
+  }
   if (xowner != nullptr) {
     hipLaunchKernelGGL(topk_scan_fp4_owned_kernel, grid, dim3(512), 0, cur_stream(),
                        Q4.data_ptr<uint8_t>(), QS.data_ptr<uint8_t>(),
@@ -515,6 +559,21 @@ std::vector<torch::Tensor> topk_scan_threshold_fp4x4_owned(
     int64_t n_swaths) {
   return fp4x4_scan(Q4, QS, X4, XS, theta, cap, n_swaths, -1, false, &xowner,
                     &qowner);
+}
+
+// fp4x4 threshold scan (v10, or the owned scan with owners) that returns a
+// fourth tensor hist[nq, 256] int32, zeroed here: per query, the hits that
+// found the candidate buffer full, counted in bins of width w[q] above
+// theta[q] (ops.gpu.hist_bin_spec is the bin rule).
+std::vector<torch::Tensor> topk_scan_threshold_fp4x4_hist(
+    torch::Tensor Q4, torch::Tensor QS, torch::Tensor X4, torch::Tensor XS,
+    torch::Tensor theta, torch::Tensor w, int64_t cap, int64_t n_swaths,
+    c10::optional<torch::Tensor> xowner, c10::optional<torch::Tensor> qowner) {
+  TORCH_CHECK(xowner.has_value() == qowner.has_value(),
+              "xowner and qowner must be given together");
+  bool owned = xowner.has_value();
+  return fp4x4_scan(Q4, QS, X4, XS, theta, cap, n_swaths, -1, false,
+                    owned ? &*xowner : nullptr, owned ? &*qowner : nullptr, &w);
 }
 
 std::vector<torch::Tensor> topk_scan_threshold(torch::Tensor Q, torch::Tensor X,
@@ -877,6 +936,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Q4"), py::arg("QS"), py::arg("X4"), py::arg("XS"),
         py::arg("theta"), py::arg("xowner"), py::arg("qowner"), py::arg("cap"),
         py::arg("n_swaths"));
+  m.def("topk_scan_threshold_fp4x4_hist", &topk_scan_threshold_fp4x4_hist,
+        "full-MXFP4 threshold scan + per-query histogram of the dropped hits",
+        py::arg("Q4"), py::arg("QS"), py::arg("X4"), py::arg("XS"),
+        py::arg("theta"), py::arg("w"), py::arg("cap"), py::arg("n_swaths"),
+        py::arg("xowner") = c10::nullopt, py::arg("qowner") = c10::nullopt);
   m.def("quantize_fp4_mx", &quantize_fp4_mx,
         "fused bf16 -> MXFP4 (fragment order) quantize, bit-exact with to_fp4_mx",
         py::arg("X"), py::arg("out4") = c10::nullopt, py::arg("outs") = c10::nullopt);

@@ -2215,17 +2215,47 @@ DEVINL void fp4v9_pair(f32x4 (&acc)[8][4], uint32_t xaddr, uint32_t qaddr,
 // destination stays lane-linear, and every accumulator sees the same
 // operands in the same order: bit-identical to v9 and v1.
 //
-// One body serves three kernels, which differ in nothing else:
+// One body serves five kernels, which differ in nothing else:
 //   topk_scan_fp4_v9_kernel     SWZ = 0, unfiltered
 //   topk_scan_fp4_v10_kernel    SWZ = 1, unfiltered
 //   topk_scan_fp4_owned_kernel  SWZ = 1, owner-filtered (prologue, row-owner
 //                               loads and two-gate epilogue described at
 //                               the kernel)
+//   topk_scan_fp4_hist_kernel, topk_scan_fp4_owned_hist_kernel
+//                               the two above with HIST: a hit that finds
+//                               its query's buffer full is counted in a
+//                               per-query score histogram (hist_bin below)
+//                               instead of vanishing. HIST = false compiles
+//                               to the instructions it compiled to before
+//                               the parameter existed.
 // ---------------------------------------------------------------------------
 
 typedef int32_t i32x4_own __attribute__((ext_vector_type(4)));
 
-template <int SWZ, bool OWNED>
+// Histogram of the hits that found the candidate buffer full (HIST bodies):
+// HIST_NB bins of width w above theta, per query. edge(j) = fp32(fp64(j) *
+// fp64(w) + fp64(theta)); bin(v) is the b with edge(b) < v <= edge(b + 1),
+// the last bin open above. The bin is estimated from (v - theta) * inv_w,
+// clamped as a float (fmax drops a NaN, fmin an inf) ahead of the int
+// conversion, then moved by at most one bin against the two edges. The rule
+// is ops.gpu.hist_bin_spec, bit for bit; j * w is exact in fp64, so a
+// contracted fma gives the same edge as the spec's multiply and add.
+#define HIST_NB 256
+
+DEVINL float hist_edge(int j, float w, float theta) {
+  return (float)((double)j * (double)w + (double)theta);
+}
+
+DEVINL int hist_bin(float v, float theta, float w, float inv_w) {
+  float t = (v - theta) * inv_w;
+  t = __builtin_fminf(__builtin_fmaxf(t, 0.0f), (float)(HIST_NB - 1));
+  int b = (int)t;
+  if (b > 0 && !(v > hist_edge(b, w, theta))) b -= 1;
+  else if (b < HIST_NB - 1 && v > hist_edge(b + 1, w, theta)) b += 1;
+  return b;
+}
+
+template <int SWZ, bool OWNED, bool HIST>
 DEVINL void fp4_scan_body(const uint8_t* __restrict__ Q4, const uint8_t* __restrict__ QS,
                           const uint8_t* __restrict__ X4, const uint8_t* __restrict__ XS,
                           int nq, int nx, int D, int k, int n_swaths,
@@ -2234,7 +2264,14 @@ DEVINL void fp4_scan_body(const uint8_t* __restrict__ Q4, const uint8_t* __restr
                           const float* __restrict__ theta,
                           int32_t* __restrict__ tc_n, int cap,
                           const int32_t* __restrict__ xowner,
-                          const int32_t* __restrict__ qowner) {
+                          const int32_t* __restrict__ qowner,
+                          // HIST only: hist[nq][HIST_NB] counts, by score
+                          // bin, the hits that found the buffer full;
+                          // hist_w / hist_iw are the per-query bin width
+                          // and its reciprocal
+                          int32_t* __restrict__ hist,
+                          const float* __restrict__ hist_w,
+                          const float* __restrict__ hist_iw) {
   __shared__ bf16 lds_q[4 * BM * BK];
   __shared__ bf16 lds_x[4 * BN * BK];
   __shared__ __attribute__((aligned(16))) uint8_t lds_qs[BM * SCALE9_PITCH];
@@ -2483,6 +2520,12 @@ DEVINL void fp4_scan_body(const uint8_t* __restrict__ Q4, const uint8_t* __restr
           if (pos < cap) {
             cand_scores[grow * cap + pos] = v;
             cand_ids[grow * cap + pos] = int32_t(col);
+          } else if constexpr (HIST) {
+            // dropped hit: count it by score bin. Pointer and per-query
+            // loads are formed here, behind the laundered row index, so
+            // queries that fit their buffer pay nothing.
+            int b = hist_bin(v, th[m][r], hist_w[grow], hist_iw[grow]);
+            atomicAdd(&hist[grow * HIST_NB + b], 1);
           }
         }
   }
@@ -2498,8 +2541,9 @@ topk_scan_fp4_v9_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
                         int32_t* __restrict__ cand_ids,
                         const float* __restrict__ theta,
                         int32_t* __restrict__ tc_n, int cap) {
-  fp4_scan_body<0, false>(Q4, QS, X4, XS, nq, nx, D, k, n_swaths, cand_scores,
-                          cand_ids, theta, tc_n, cap, nullptr, nullptr);
+  fp4_scan_body<0, false, false>(Q4, QS, X4, XS, nq, nx, D, k, n_swaths,
+                                 cand_scores, cand_ids, theta, tc_n, cap, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr);
 }
 
 extern "C" __global__ void __launch_bounds__(TK_THREADS)
@@ -2510,8 +2554,28 @@ topk_scan_fp4_v10_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restri
                          int32_t* __restrict__ cand_ids,
                          const float* __restrict__ theta,
                          int32_t* __restrict__ tc_n, int cap) {
-  fp4_scan_body<1, false>(Q4, QS, X4, XS, nq, nx, D, k, n_swaths, cand_scores,
-                          cand_ids, theta, tc_n, cap, nullptr, nullptr);
+  fp4_scan_body<1, false, false>(Q4, QS, X4, XS, nq, nx, D, k, n_swaths,
+                                 cand_scores, cand_ids, theta, tc_n, cap, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr);
+}
+
+// v10 with the dropped-hit histogram (overflow="rescan" of the threshold
+// recall): the same body, HIST = true. The only extra device code is the
+// else of the buffer-full test in the slow path.
+extern "C" __global__ void __launch_bounds__(TK_THREADS)
+topk_scan_fp4_hist_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restrict__ QS,
+                          const uint8_t* __restrict__ X4, const uint8_t* __restrict__ XS,
+                          int nq, int nx, int D, int k, int n_swaths,
+                          float* __restrict__ cand_scores,
+                          int32_t* __restrict__ cand_ids,
+                          const float* __restrict__ theta,
+                          int32_t* __restrict__ tc_n, int cap,
+                          int32_t* __restrict__ hist,
+                          const float* __restrict__ hist_w,
+                          const float* __restrict__ hist_iw) {
+  fp4_scan_body<1, false, true>(Q4, QS, X4, XS, nq, nx, D, k, n_swaths,
+                                cand_scores, cand_ids, theta, tc_n, cap, nullptr,
+                                nullptr, hist, hist_w, hist_iw);
 }
 
 // ===========================================================================
@@ -2723,7 +2787,27 @@ topk_scan_fp4_owned_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __rest
                            int32_t* __restrict__ tc_n, int cap,
                            const int32_t* __restrict__ xowner,
                            const int32_t* __restrict__ qowner) {
-  fp4_scan_body<1, true>(Q4, QS, X4, XS, nq, nx, D, k, n_swaths, cand_scores,
-                         cand_ids, theta, tc_n, cap, xowner, qowner);
+  fp4_scan_body<1, true, false>(Q4, QS, X4, XS, nq, nx, D, k, n_swaths,
+                                cand_scores, cand_ids, theta, tc_n, cap, xowner,
+                                qowner, nullptr, nullptr, nullptr);
+}
+
+// the owner-filtered scan with the dropped-hit histogram
+extern "C" __global__ void __launch_bounds__(TK_THREADS)
+topk_scan_fp4_owned_hist_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restrict__ QS,
+                                const uint8_t* __restrict__ X4, const uint8_t* __restrict__ XS,
+                                int nq, int nx, int D, int k, int n_swaths,
+                                float* __restrict__ cand_scores,
+                                int32_t* __restrict__ cand_ids,
+                                const float* __restrict__ theta,
+                                int32_t* __restrict__ tc_n, int cap,
+                                const int32_t* __restrict__ xowner,
+                                const int32_t* __restrict__ qowner,
+                                int32_t* __restrict__ hist,
+                                const float* __restrict__ hist_w,
+                                const float* __restrict__ hist_iw) {
+  fp4_scan_body<1, true, true>(Q4, QS, X4, XS, nq, nx, D, k, n_swaths,
+                               cand_scores, cand_ids, theta, tc_n, cap, xowner,
+                               qowner, hist, hist_w, hist_iw);
 }
 

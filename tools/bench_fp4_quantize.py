@@ -19,6 +19,12 @@
              ingested rows) and random-letter messages (no clusters). Also
              prints per-stage hipEvent ms and how many queries per step took
              the direct-kernel fallback of the threshold recall.
+             --overflow direct|rescan|direct,rescan picks
+             PipelineConfig.recall_overflow; with both, every round runs the
+             two modes one after the other (alternating), ingest on only,
+             and each line carries recall ms per step and the pipeline's
+             recall_overflowed / recall_rescanned / recall_direct_fallbacks
+             per step. Results: profiles/README.md, "recall overflow rescan".
   forget     forgetting at the index shape (--index x --dim, 50M x 1024):
              1 % of the rows evicted from a salience vector with realistic
              ties. evict_mask and forget_plan ms; the move kernel
@@ -149,14 +155,21 @@ def mode_ingest(args):
     make = {"synthetic": lambda i: synthetic_batch(args.batch, seed=i),
             "random": lambda i: random_batch(args.batch, i)}
     total = args.steps + args.warmup
-    variants = [(c, v) for _ in range(args.rounds) for c in args.content.split(",")
-                for v in ("off", "off+read", "on")]
-    for content, v in variants:
+    modes = args.overflow.split(",")
+    for m in modes:
+        if m not in ("direct", "rescan"):
+            raise SystemExit(f"--overflow: unknown mode {m!r}")
+    # comparing the two overflow modes: ingest on only, the modes alternate
+    ingest_variants = ("on",) if len(modes) > 1 else ("off", "off+read", "on")
+    variants = [(c, v, m) for _ in range(args.rounds) for c in args.content.split(",")
+                for v in ingest_variants for m in modes]
+    for content, v, overflow in variants:
         pool = [make[content](i) for i in range(4)]
         del fallback[:]
         cfg = PipelineConfig(batch=args.batch, dim=args.dim, index_size=shard,
                              ingest=(v == "on"),
-                             ingest_capacity=(total + 3) * args.batch)
+                             ingest_capacity=(total + 3) * args.batch,
+                             recall_overflow=overflow)
         pipe = FirewallPipeline(cfg, device="cuda:0")
         ring = StagingRing(pipe, max_bytes=8 << 20, max_msgs=max(args.batch, 8192) + 1)
         nxt = ring.stage(pool[0])
@@ -172,6 +185,8 @@ def mode_ingest(args):
         torch.cuda.synchronize()
         ms = (time.perf_counter() - t0) / args.steps * 1000
         rows_after, fb = pipe.n_rows, sum(fallback) / total
+        counters = {k: round(getattr(pipe, k) / total, 1) for k in
+                    ("recall_overflowed", "recall_rescanned", "recall_direct_fallbacks")}
         # per-stage timing outside the timed loop (the profiler synchronizes)
         pipe.profiler.enabled = True
         for i in range(3):
@@ -179,7 +194,10 @@ def mode_ingest(args):
             pipe.profiler.commit()
         stages = {k: round(x, 3) for k, x in pipe.profiler.summary().items()}
         print(json.dumps({"mode": "ingest", "content": content, "variant": v,
-                          "ms_per_step": round(ms, 3), "rows_after": rows_after,
+                          "overflow": overflow, "ms_per_step": round(ms, 3),
+                          "recall_ms_per_step": stages.get("recall"),
+                          **{k + "_per_step": x for k, x in counters.items()},
+                          "rows_after": rows_after,
                           "dropped": pipe.ingest_dropped, "index_rows": shard,
                           "batch": args.batch, "fallback_queries_per_step": round(fb, 1),
                           "stage_ms": stages}), flush=True)
@@ -319,6 +337,9 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--overflow", default="direct",
+                    help="ingest mode: PipelineConfig.recall_overflow, direct, rescan "
+                         "or direct,rescan (alternating)")
     ap.add_argument("--content", default="synthetic,random",
                     help="ingest and forget modes: comma list of synthetic, random")
     args = ap.parse_args()

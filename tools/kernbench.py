@@ -202,9 +202,49 @@ def fp4_owned_scan_bench(n_owners, iters=9):
               f"{2*nq*rows*dim/1e12/ms*1000:7.1f} TF/s   hits {hits}")
 
 
+def fp4_hist_scan_bench(iters=9, rounds=3):
+    """What the dropped-hit histogram costs a scan that drops nothing: the
+    v10 scan against topk_scan_fp4_hist_kernel, and the owned scan (1 owner)
+    against topk_scan_fp4_owned_hist_kernel, at the fp4_scan_bench shape and
+    theta (no query overflows cap = 1024), alternating, `rounds` rounds of
+    medians of `iters`."""
+    torch.manual_seed(7)
+    dev = "cuda:0"
+    rows, nq, dim, cap = 4_194_304, 4096, 1024, 1024
+    X = torch.nn.functional.normalize(torch.randn(rows, dim, device=dev), dim=1).bfloat16()
+    Q = torch.nn.functional.normalize(torch.randn(nq, dim, device=dev), dim=1).bfloat16()
+    X4, XS = g.to_fp4_mx(X)
+    Q4, QS = g.to_fp4_mx(Q)
+    s = torch.matmul(Q, X[:65536].T).float()
+    theta = (s.mean(dim=1) + 4.2 * s.std(dim=1)).contiguous()
+    del X, s
+    w = ((1.0625 - theta) / g.HIST_NB).contiguous()
+    xo = torch.zeros(rows, dtype=torch.int32, device=dev)
+    qo = torch.zeros(nq, dtype=torch.int32, device=dev)
+    e = g.ext()
+    configs = [
+        ("v10", lambda: e.topk_scan_threshold_fp4x4(Q4, QS, X4, XS, theta, cap, 0, 10, False)),
+        ("v10 + hist", lambda: e.topk_scan_threshold_fp4x4_hist(
+            Q4, QS, X4, XS, theta, w, cap, 0)),
+        ("owned", lambda: e.topk_scan_threshold_fp4x4_owned(
+            Q4, QS, X4, XS, theta, xo, qo, cap, 0)),
+        ("owned + hist", lambda: e.topk_scan_threshold_fp4x4_hist(
+            Q4, QS, X4, XS, theta, w, cap, 0, xowner=xo, qowner=qo)),
+    ]
+    for rnd in range(rounds):
+        for name, fn in configs:
+            ms = timed_median(fn, iters=iters)
+            out = fn()
+            print(f"fp4x4 round {rnd} {name:14s} {ms:9.3f} ms (median of {iters})   "
+                  f"hits {int(out[2].sum())}   max/query {int(out[2].max())}   "
+                  f"hist {int(out[3].sum()) if len(out) > 3 else '-'}")
+
+
 if __name__ == "__main__":
     import sys as _sys
-    if "--fp4-scan" in _sys.argv and "--owners" in _sys.argv:
+    if "--fp4-scan" in _sys.argv and "--hist" in _sys.argv:
+        fp4_hist_scan_bench()
+    elif "--fp4-scan" in _sys.argv and "--owners" in _sys.argv:
         fp4_owned_scan_bench(int(_sys.argv[_sys.argv.index("--owners") + 1]))
     elif "--fp4-scan" in _sys.argv:
         fp4_scan_bench()

@@ -596,6 +596,154 @@ def audit_pack(
     )
 
 
+HIST_NB = 256  # csrc/topk_recall.hip HIST_NB
+
+
+def hist_edges(theta: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """[nq, HIST_NB + 1] fp32 bin edges of the dropped-hit histogram:
+    edge(j) = fp32(fp64(j) * fp64(w) + fp64(theta)). edge(HIST_NB) bounds
+    nothing (the last bin is open above); it is there so that edge(b + 1)
+    exists for every bin."""
+    j = torch.arange(HIST_NB + 1, dtype=torch.float64, device=theta.device)
+    e = j.unsqueeze(0) * w.double().unsqueeze(1) + theta.double().unsqueeze(1)
+    return e.float()
+
+
+def hist_bin_spec(v: torch.Tensor, theta: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """The bin rule of the hist scan kernels (csrc/topk_recall.hip hist_bin),
+    bit for bit, in torch; device agnostic (CPU tensors included). `v` is
+    [nq, n] fp32 scores above theta, `theta` and `w` are [nq] fp32, w > 0.
+    Returns int64 bins in [0, HIST_NB).
+
+    bin(v) is the b with edge(b) < v <= edge(b + 1) (hist_edges); bin 0 also
+    takes everything down to theta and the last bin is open above. The bin
+    is estimated from (v - theta) * (1 / w), clamped as a float ahead of the
+    int conversion (fmax drops a NaN, fmin an inf), then moved by at most one
+    bin against edge(b) and edge(b + 1). The estimate is within one bin of
+    the rule as long as w spans a few ulps of theta and of the scores; for a
+    smaller w the result is still this function's, in the kernel too, but
+    neighbouring edges coincide and the rule above has no single answer."""
+    v = v.float()
+    th = theta.float().unsqueeze(1)
+    inv_w = (1.0 / w.float()).unsqueeze(1)
+    t = (v - th) * inv_w
+    t = torch.fmin(torch.fmax(t, t.new_zeros(())), t.new_full((), float(HIST_NB - 1)))
+    b = t.to(torch.int64)
+    edges = hist_edges(theta.float(), w.float())
+    lo = edges.gather(1, b)
+    hi = edges.gather(1, b + 1)
+    down = (b > 0) & ~(v > lo)
+    up = ~down & (b < HIST_NB - 1) & (v > hi)
+    return b - down.long() + up.long()
+
+
+def overflow_rescan_plan(
+    cand_scores: torch.Tensor,
+    counts: torch.Tensor,
+    hist: torch.Tensor,
+    theta: torch.Tensor,
+    w: torch.Tensor,
+    cap: int,
+    need,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Where to rescan the queries that overflowed their candidate buffer.
+    Inputs are the outputs of the hist scan (topk_scan_threshold_fp4x4_hist)
+    and its theta / w; `need` is an int or an [nq] tensor, the number of
+    hits a query has to keep. Pure torch, device agnostic.
+
+    For a query with counts > cap the cap retained scores plus the histogram
+    of the dropped hits are the whole score distribution above theta:
+    H = hist + bins of the retained scores, cum[j] = sum of H[i] for i >= j,
+    b* = the lowest j with cum[j] <= cap (the largest candidate set that
+    fits), theta2 = edge(b*), expect_n = cum[b*], ok = expect_n >= need. The
+    edge and the scan's v > theta2 are the same fp32 comparison, so a rescan
+    at theta2 appends exactly expect_n hits. Where even the last bin holds
+    more than cap hits nothing fits: theta2 = +inf, expect_n = 0, ok False.
+
+    Queries with counts <= cap are left untouched: theta2 = theta, expect_n
+    = counts, ok False (nothing to rescan). Returns (theta2 fp32 [nq],
+    expect_n int64 [nq], ok bool [nq])."""
+    nq = counts.shape[0]
+    over = counts > cap
+    b = hist_bin_spec(cand_scores, theta, w)
+    H = hist.to(torch.int64).clone()
+    H.scatter_add_(1, b, torch.ones_like(b))
+    cum = H.flip(1).cumsum(1).flip(1)
+    # cum falls with j, so the bins that fit are a suffix
+    bstar = HIST_NB - (cum <= cap).sum(dim=1)
+    none = bstar == HIST_NB
+    cum = torch.cat([cum, cum.new_zeros(nq, 1)], dim=1)
+    expect = cum.gather(1, bstar.unsqueeze(1)).squeeze(1)
+    theta = theta.float()
+    edge = hist_edges(theta, w.float()).gather(1, bstar.unsqueeze(1)).squeeze(1)
+    edge = torch.where(none, torch.full_like(edge, float("inf")), edge)
+    if not torch.is_tensor(need):
+        need = torch.full_like(expect, int(need))
+    theta2 = torch.where(over, edge, theta)
+    expect_n = torch.where(over, expect, counts.to(torch.int64))
+    ok = over & (expect >= need.to(torch.int64))
+    return theta2, expect_n, ok
+
+
+def fp4x4_rescan(Q4, QS, X4, theta2, rows, cap, owner=None, qowner=None, n_swaths=0):
+    """Scan the query rows `rows` (int64 [n]) of Q4 / QS again, at
+    theta2[rows], with the plain v10 scan (the owned scan with owners).
+    Returns (cand_scores, cand_ids, counts) of those n rows.
+
+    Scan scores do not depend on which queries share a block, with one
+    exception: the scans stage the query scale sheet in 16 B pieces and
+    clamp the last piece into the array, so when nq * D/32 is not a multiple
+    of 16 the last rows are scored with their neighbours' scales (the clamp
+    rule noted in docs/NOTES-NEXT.md; D = 512 and 1024 are never affected).
+    The gathered block is therefore padded to a multiple of 4 rows, by
+    repeating the last row, and the padding dropped from the result."""
+    n = int(rows.numel())
+    pad = (-n) % 4
+    if pad:
+        rows = torch.cat([rows, rows[-1:].expand(pad)])
+    q4r, qsr = Q4[rows].contiguous(), QS[rows].contiguous()
+    th2 = theta2[rows].contiguous()
+    if owner is None:
+        out = ext().topk_scan_threshold_fp4x4(q4r, qsr, X4[0], X4[1], th2, cap, n_swaths)
+    else:
+        out = ext().topk_scan_threshold_fp4x4_owned(
+            q4r, qsr, X4[0], X4[1], th2, owner, qowner[rows].contiguous(), cap, n_swaths)
+    return tuple(t[:n] for t in out)
+
+
+def _scan_fp4x4_rescan(Q, Q4, QS, X4, theta, cap, x_norm_bound, owner, qowner, need):
+    """The fp4x4 threshold scan with overflow="rescan" (topk_recall_threshold):
+    hist scan, plan, rescan of the overflowed queries that the plan can
+    place, results scattered back. Returns (cand_scores, cand_ids, counts,
+    overflowed, rescanned), the last two as host ints."""
+    # bins span theta .. hi; any hi is safe (the last bin is open above).
+    # Where that leaves w under a few ulps of the scores (or hi <= theta,
+    # or theta = +inf) the bin edges would coincide: a tiny w then puts
+    # every hit into the last bin and the query ends at ok = False.
+    hi = Q.float().norm(dim=1) * (float(x_norm_bound) * 1.0625)
+    w = (hi - theta) / HIST_NB
+    floor = torch.maximum(theta.abs(), hi.abs()) * 2.0 ** -20
+    w = torch.where(w > floor, w, torch.full_like(w, 1e-30)).contiguous()
+    if owner is None:
+        cs, ci, counts, hist = ext().topk_scan_threshold_fp4x4_hist(
+            Q4, QS, X4[0], X4[1], theta, w, cap, 0)
+    else:
+        cs, ci, counts, hist = ext().topk_scan_threshold_fp4x4_hist(
+            Q4, QS, X4[0], X4[1], theta, w, cap, 0, xowner=owner, qowner=qowner)
+    n_over = int((counts > cap).sum())
+    if n_over == 0:
+        return cs, ci, counts, 0, 0
+    theta2, _expect_n, ok = overflow_rescan_plan(cs, counts, hist, theta, w, cap, need)
+    rows = ok.nonzero(as_tuple=True)[0]
+    n_rows = int(rows.numel())
+    if n_rows:
+        cs2, ci2, cn2 = fp4x4_rescan(Q4, QS, X4, theta2, rows, cap, owner, qowner)
+        cs[rows] = cs2
+        ci[rows] = ci2
+        counts[rows] = cn2
+    return cs, ci, counts, n_over, n_rows
+
+
 def topk_recall_threshold(
     Q: torch.Tensor,
     X: torch.Tensor,
@@ -611,6 +759,9 @@ def topk_recall_threshold(
     owner: Optional[torch.Tensor] = None,
     qowner: Optional[torch.Tensor] = None,
     owner_counts: Optional[torch.Tensor] = None,
+    overflow: str = "direct",
+    x_norm_bound: float = 1.0,
+    stats: Optional[dict] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Threshold-scan recall: per-query score thresholds estimated from a
     sampled pre-pass (Gaussian tail extrapolation), then a fixed-threshold
@@ -630,7 +781,25 @@ def topk_recall_threshold(
     = cached bincount of `owner`), every candidate is already eligible, and
     the fallback is the owner-filtered direct kernel. Supported by the
     fp4x4 scan (q4, D <= 1024) and the bf16 scan.
+
+    `overflow` is what happens to a query with more than `cap` hits above
+    its threshold (clustered content: the Gaussian tail does not describe
+    it). "direct" sends it to the direct kernel over the whole index.
+    "rescan" (fp4x4 scan only: q4, D <= 1024, with or without owners) has
+    the scan count the hits it drops in a 256-bin score histogram per query
+    (csrc topk_scan_fp4_hist_kernel; bins span theta .. |q| * x_norm_bound *
+    1.0625, scores past that land in the open last bin), picks from it the
+    lowest bin edge above which at most `cap` hits lie
+    (overflow_rescan_plan) and rescans only those queries at that threshold,
+    which then fits exactly. `x_norm_bound` bounds the row norms of X. A
+    query whose top `cap` hits sit inside one bin with fewer than k above it
+    still goes to the direct kernel, as underflowed queries do.
+
+    `stats`, if a dict, receives the number of queries that `overflowed`,
+    were `rescanned` and took the `direct_fallback`, in both modes.
     """
+    if overflow not in ("direct", "rescan"):
+        raise ValueError(f"overflow must be 'direct' or 'rescan', not {overflow!r}")
     nq, D = Q.shape
     nx = X.shape[0]
     m = min(nx, sample_rows)
@@ -641,6 +810,10 @@ def topk_recall_threshold(
     if owner is not None and use_fp8 and not (use_fp4 and q4 and D <= 1024):
         raise NotImplementedError(
             "owner-filtered recall: fp4x4 (q4, D <= 1024) and bf16 scans only")
+    rescan = overflow == "rescan"
+    if rescan and not (use_fp4 and q4 and D <= 1024):
+        raise NotImplementedError(
+            "overflow='rescan': fp4x4 scan (q4, D <= 1024) only")
 
     # 1. per-query score statistics from a sample (bf16 matmul)
     sample = torch.matmul(Q, X[:m].T).float()  # [nq, m]
@@ -690,7 +863,11 @@ def topk_recall_threshold(
         # both operands MXFP4: scores carry no static prescale
         # (one fused launch, bit-exact with to_fp4_mx)
         Q4, QS = quantize_fp4_mx(Q)
-        if owner is None:
+        if rescan:
+            cs, ci, counts, n_over, n_rescanned = _scan_fp4x4_rescan(
+                Q, Q4, QS, X4, theta, cap, x_norm_bound, owner, qowner,
+                k if owner is None else n_owned.clamp_max(k))
+        elif owner is None:
             cs, ci, counts = ext().topk_scan_threshold_fp4x4(
                 Q4, QS, X4[0], X4[1], theta.contiguous(), cap, 0)
         else:
@@ -751,7 +928,16 @@ def topk_recall_threshold(
         # an owner with fewer than k rows legitimately underfills: those
         # queries are done once every owned row is a candidate
         bad = (counts < n_owned.clamp_max(k)) | (counts > cap)
-    if bool(bad.any()):
+    if stats is None:
+        any_bad = bool(bad.any())
+    else:
+        # one host read for both figures
+        n_of, n_bad = torch.stack([(counts > cap).sum(), bad.sum()]).tolist()
+        stats["overflowed"] = n_over if rescan else n_of
+        stats["rescanned"] = n_rescanned if rescan else 0
+        stats["direct_fallback"] = n_bad
+        any_bad = n_bad > 0
+    if any_bad:
         rows = bad.nonzero(as_tuple=True)[0]
         k2f = min(4 * k, 32, X.shape[0])  # the direct kernel's k bound
         if owner is None:

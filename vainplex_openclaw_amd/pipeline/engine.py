@@ -18,7 +18,9 @@ messages:
   4. classifier head (csrc/gemm_nt.hip, fused sigmoid): injection /
      threat logits
   5. Membrane recall (csrc/topk_recall.hip): cosine top-k against the
-     HBM-resident embedding index shard
+     HBM-resident embedding index shard; cfg.recall_overflow picks what a
+     query with more hits than the candidate buffer costs (direct kernel,
+     or in-scan histogram + rescan)
   6. firewall verdict + trust updates (csrc/firewall.hip) implementing
      the reference's risk weights / verdict precedence / trust formula
   7. audit: 64-B records packed on GPU, SHA-256 leaves + Merkle root
@@ -112,6 +114,14 @@ class PipelineConfig:
     # once in many steps. Ignored without ingest.
     ingest_full: str = "drop"
     evict_frac: float = 0.01
+    # what the threshold recall does with a query that has more hits above
+    # its threshold than the candidate buffer holds (clustered, ingested
+    # content): "direct" redoes it with the direct kernel over the whole
+    # index; "rescan" has the fp4 scan histogram the hits it drops and
+    # rescans only those queries at a threshold known to fit
+    # (ops.gpu.topk_recall_threshold overflow=). threshold and
+    # threshold_banded modes on the fp4 index.
+    recall_overflow: str = "direct"
 
 
 class StageProfiler:
@@ -188,6 +198,18 @@ class FirewallPipeline:
             self.ingest_dropped = 0
             if cfg.ingest and cfg.ingest_full not in ("drop", "evict"):
                 raise ValueError(f"ingest_full must be 'drop' or 'evict', not {cfg.ingest_full!r}")
+            if cfg.recall_overflow not in ("direct", "rescan"):
+                raise ValueError(
+                    f"recall_overflow must be 'direct' or 'rescan', not {cfg.recall_overflow!r}")
+            if cfg.recall_overflow == "rescan" and not (fp4_index and cfg.dim <= 1024):
+                raise ValueError("recall_overflow='rescan': threshold recall on the fp4 "
+                                 "index (recall_fp4, dim % 128 == 0, dim <= 1024) only")
+            # threshold recall, cumulative over the steps, in queries: how
+            # many overflowed their candidate buffer, were rescanned at a
+            # raised threshold, went to the direct kernel (over- or underflow)
+            self.recall_overflowed = 0
+            self.recall_rescanned = 0
+            self.recall_direct_fallbacks = 0
             # rows forgotten so far, and the number of forgets that moved
             # rows: recall_ids from before a forget name rows as they were
             self.forgotten = 0
@@ -484,22 +506,32 @@ class FirewallPipeline:
         if self.index_owner is not None:
             own = {"owner": self.index_owner[:n_live], "owner_counts": self.owner_counts}
 
+        rstats: Dict[str, int] = {}
+
+        def count_recall(res):
+            self.recall_overflowed += rstats["overflowed"]
+            self.recall_rescanned += rstats["rescanned"]
+            self.recall_direct_fallbacks += rstats["direct_fallback"]
+            return res
+
         def local_recall(queries, qowner=None):
             if qowner is not None:
                 own["qowner"] = qowner
             if cfg.recall_mode == "threshold_banded" and sal is not None:
                 if self._steps_done and self._steps_done % cfg.band_refresh_steps == 0:
                     self._refresh_hot_band()
-                return g.topk_recall_threshold_banded(
+                return count_recall(g.topk_recall_threshold_banded(
                     queries, index, cfg.topk, salience=sal,
                     hot_idx=self.hot_idx, hot_X=self.hot_X, is_hot=self.is_hot[:n_live],
-                    X8=self.index8, mx=cfg.recall_mx, X4=index4, **own,
-                )
+                    X8=self.index8, mx=cfg.recall_mx, X4=index4,
+                    overflow=cfg.recall_overflow, stats=rstats, **own,
+                ))
             if cfg.recall_mode in ("threshold", "threshold_banded"):
-                return g.topk_recall_threshold(
+                return count_recall(g.topk_recall_threshold(
                     queries, index, cfg.topk, X8=self.index8,
-                    mx=cfg.recall_mx, X4=index4, salience=sal, **own
-                )
+                    mx=cfg.recall_mx, X4=index4, salience=sal,
+                    overflow=cfg.recall_overflow, stats=rstats, **own
+                ))
             if cfg.recall_mode == "two_stage" and self.index8 is not None:
                 return g.topk_recall_two_stage(queries, index, self.index8,
                                                cfg.topk, salience=sal)
