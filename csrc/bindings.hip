@@ -96,6 +96,11 @@ __global__ void fp4_quantize_append_kernel(const uint16_t*, const int32_t*, int,
                                            int32_t*, const int32_t*, float*, float);
 __global__ void index_move_rows_kernel(const int32_t*, const int32_t*, long long, int, int,
                                        uint4*, uint4*, uint32_t*, uint32_t*, uint32_t*);
+__global__ void batch_first_similar_kernel(const __bf16*, const uint8_t*, const int32_t*,
+                                           int, int, float, int32_t*);
+__global__ void recall_dup_rows_kernel(const uint4*, const int32_t*, const uint4*,
+                                       const int32_t*, const int32_t*, int, int, int, int,
+                                       float, int32_t*, float*);
 struct AuditRecord64;
 __global__ void audit_pack_kernel(const int8_t*, const float*, const unsigned long long*,
                                   const unsigned long long*, const int32_t*, const float*,
@@ -835,6 +840,90 @@ void index_move_rows(torch::Tensor src, torch::Tensor dst,
                      (int)cap, D, ip, x4p, xsp, op, sp);
 }
 
+// -- ingest dedup: near-duplicate detection (csrc/ingest_dedup.hip) --------
+
+void batch_first_similar(torch::Tensor F, torch::Tensor elig, double tau,
+                         c10::optional<torch::Tensor> owner, torch::Tensor first) {
+  // first[i] <- min(first[i], smallest eligible same-owner j < i with
+  // dot(F_i, F_j) >= tau); the caller presets first (i if eligible, else -1)
+  CHECK_GPU(F); CHECK_CONTIG(F); CHECK_GPU(elig); CHECK_CONTIG(elig);
+  CHECK_GPU(first); CHECK_CONTIG(first);
+  TORCH_CHECK(F.dtype() == torch::kBFloat16 && F.dim() == 2, "F must be bf16 [B, D]");
+  long long B = F.size(0);
+  int D = F.size(1);
+  TORCH_CHECK(B >= 1 && B <= (1LL << 22), "batch_first_similar needs 1 <= B <= 2^22");
+  TORCH_CHECK(D > 0 && D % 32 == 0, "batch_first_similar needs D % 32 == 0");
+  TORCH_CHECK(aligned16(F), "F must be 16-byte aligned");
+  TORCH_CHECK((elig.dtype() == torch::kBool || elig.dtype() == torch::kUInt8) &&
+              elig.dim() == 1 && elig.numel() == B, "elig must be bool [B]");
+  TORCH_CHECK(first.dtype() == torch::kInt32 && first.dim() == 1 && first.numel() == B,
+              "first must be int32 [B]");
+  TORCH_CHECK(elig.device() == F.device() && first.device() == F.device(),
+              "F, elig and first on different devices");
+  const int32_t* op = nullptr;
+  if (owner.has_value()) {
+    CHECK_GPU((*owner)); CHECK_CONTIG((*owner));
+    TORCH_CHECK(owner->dtype() == torch::kInt32 && owner->dim() == 1 && owner->numel() == B,
+                "owner must be int32 [B]");
+    TORCH_CHECK(owner->device() == F.device(), "F and owner on different devices");
+    op = owner->data_ptr<int32_t>();
+  }
+  unsigned tiles = (unsigned)((B + 127) / 128);
+  hipLaunchKernelGGL(batch_first_similar_kernel, dim3(tiles, tiles), dim3(256), 0,
+                     cur_stream(), reinterpret_cast<const __bf16*>(F.data_ptr()),
+                     reinterpret_cast<const uint8_t*>(elig.data_ptr()), op, (int)B, D,
+                     (float)tau, first.data_ptr<int32_t>());
+}
+
+std::vector<torch::Tensor> recall_dup_rows(torch::Tensor F, torch::Tensor ids,
+                                           torch::Tensor X, double tau,
+                                           c10::optional<torch::Tensor> xowner,
+                                           c10::optional<torch::Tensor> qowner) {
+  // per message the recalled row with the largest dot >= tau (ties: lowest
+  // id), -1 if none; ids are bounds-checked by the kernel
+  CHECK_GPU(F); CHECK_CONTIG(F); CHECK_GPU(ids); CHECK_CONTIG(ids);
+  CHECK_GPU(X); CHECK_CONTIG(X);
+  TORCH_CHECK(F.dtype() == torch::kBFloat16 && F.dim() == 2, "F must be bf16 [B, D]");
+  TORCH_CHECK(X.dtype() == torch::kBFloat16 && X.dim() == 2, "X must be bf16 [n, D]");
+  long long B = F.size(0), n = X.size(0);
+  int D = F.size(1);
+  TORCH_CHECK(X.size(1) == D, "F and X differ in D");
+  TORCH_CHECK(D > 0 && D % 8 == 0 && D <= 2048, "recall_dup_rows needs D%8==0, D<=2048");
+  TORCH_CHECK(B < (1LL << 31) && n < (1LL << 31), "too many rows");
+  TORCH_CHECK(aligned16(F) && aligned16(X), "F and X must be 16-byte aligned");
+  TORCH_CHECK(ids.dtype() == torch::kInt32 && ids.dim() == 2 && ids.size(0) == B,
+              "ids must be int32 [B, k]");
+  TORCH_CHECK(ids.device() == F.device() && X.device() == F.device(),
+              "F, ids and X on different devices");
+  int k = ids.size(1);
+  TORCH_CHECK(xowner.has_value() == qowner.has_value(), "xowner and qowner go together");
+  const int32_t* xop = nullptr; const int32_t* qop = nullptr;
+  if (xowner.has_value()) {
+    CHECK_GPU((*xowner)); CHECK_CONTIG((*xowner));
+    CHECK_GPU((*qowner)); CHECK_CONTIG((*qowner));
+    TORCH_CHECK(xowner->dtype() == torch::kInt32 && qowner->dtype() == torch::kInt32,
+                "owners must be int32");
+    TORCH_CHECK(xowner->dim() == 1 && xowner->numel() == n, "xowner must be [n]");
+    TORCH_CHECK(qowner->dim() == 1 && qowner->numel() == B, "qowner must be [B]");
+    TORCH_CHECK(xowner->device() == F.device() && qowner->device() == F.device(),
+                "owners on another device than F");
+    xop = xowner->data_ptr<int32_t>();
+    qop = qowner->data_ptr<int32_t>();
+  }
+  auto dup_row = torch::empty({B}, torch::dtype(torch::kInt32).device(F.device()));
+  auto dup_dot = torch::empty({B}, torch::dtype(torch::kFloat32).device(F.device()));
+  if (B == 0) return {dup_row, dup_dot};
+  // one wave per message, 4 waves per block; cap the grid, stride the rest
+  long long blocks = (B + 3) / 4;
+  if (blocks > 256 * 8) blocks = 256 * 8;
+  hipLaunchKernelGGL(recall_dup_rows_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                     cur_stream(), reinterpret_cast<const uint4*>(F.data_ptr()),
+                     ids.data_ptr<int32_t>(), reinterpret_cast<const uint4*>(X.data_ptr()),
+                     xop, qop, (int)B, k, D, (int)n, (float)tau,
+                     dup_row.data_ptr<int32_t>(), dup_dot.data_ptr<float>());
+  return {dup_row, dup_dot};
+}
+
 void register_host_envelope(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -955,6 +1044,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("src"), py::arg("dst"), py::arg("index") = c10::nullopt,
         py::arg("X4") = c10::nullopt, py::arg("XS") = c10::nullopt,
         py::arg("owner") = c10::nullopt, py::arg("salience") = c10::nullopt);
+  m.def("batch_first_similar", &batch_first_similar,
+        "ingest dedup: lower first[i] to the earliest similar eligible row j < i",
+        py::arg("F"), py::arg("elig"), py::arg("tau"), py::arg("owner"), py::arg("first"));
+  m.def("recall_dup_rows", &recall_dup_rows,
+        "ingest dedup: per message the recalled index row with the largest dot >= tau",
+        py::arg("F"), py::arg("ids"), py::arg("X"), py::arg("tau"),
+        py::arg("xowner") = c10::nullopt, py::arg("qowner") = c10::nullopt);
   m.def("edit_distance", [](torch::Tensor bytes, torch::Tensor offsets) {
     // batched Levenshtein over string PAIRS: offsets has 2*n+1 entries;
     // pair i = strings (2i, 2i+1) in the packed byte buffer

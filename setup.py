@@ -23,6 +23,7 @@ SOURCES = [
     "csrc/topk_recall.hip",
     "csrc/fp4_quantize.hip",
     "csrc/index_forget.hip",
+    "csrc/ingest_dedup.hip",
     "csrc/firewall.hip",
     "csrc/edit_distance.hip",
     "csrc/fact_probe.hip",

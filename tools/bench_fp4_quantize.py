@@ -25,6 +25,16 @@
              and each line carries recall ms per step and the pipeline's
              recall_overflowed / recall_rescanned / recall_direct_fallbacks
              per step. Results: profiles/README.md, "recall overflow rescan".
+             --dedup TAU[,TAU...] adds one ingest-on variant per threshold
+             with PipelineConfig.ingest_dedup = TAU, alternating with plain
+             ingest on (the yardstick) in every round; every line carries
+             ingest_merged_index / ingest_merged_batch, rows_after and the
+             overflow counters. Results: profiles/README.md, "ingest dedup".
+  dedup      the two ingest-dedup kernels (csrc/ingest_dedup.hip) alone at
+             the per-step shape (--batch x --dim, k = 16 recalled ids into a
+             1M-row index): ms, hipEvent timed, on rows without duplicates,
+             on clustered rows and on a batch of identical rows (every pair
+             a hit: the most atomics the batch kernel can issue).
   forget     forgetting at the index shape (--index x --dim, 50M x 1024):
              1 % of the rows evicted from a salience vector with realistic
              ties. evict_mask and forget_plan ms; the move kernel
@@ -161,14 +171,19 @@ def mode_ingest(args):
             raise SystemExit(f"--overflow: unknown mode {m!r}")
     # comparing the two overflow modes: ingest on only, the modes alternate
     ingest_variants = ("on",) if len(modes) > 1 else ("off", "off+read", "on")
+    taus = [float(t) for t in args.dedup.split(",")] if args.dedup else []
+    if taus:
+        # against plain ingest on, the parent's step, in the same round
+        ingest_variants = ("on",) + tuple(f"on+dedup={t}" for t in taus)
     variants = [(c, v, m) for _ in range(args.rounds) for c in args.content.split(",")
                 for v in ingest_variants for m in modes]
     for content, v, overflow in variants:
         pool = [make[content](i) for i in range(4)]
         del fallback[:]
         cfg = PipelineConfig(batch=args.batch, dim=args.dim, index_size=shard,
-                             ingest=(v == "on"),
+                             ingest=v.startswith("on"),
                              ingest_capacity=(total + 3) * args.batch,
+                             ingest_dedup=float(v.partition("=")[2] or 0.0),
                              recall_overflow=overflow)
         pipe = FirewallPipeline(cfg, device="cuda:0")
         ring = StagingRing(pipe, max_bytes=8 << 20, max_msgs=max(args.batch, 8192) + 1)
@@ -185,6 +200,8 @@ def mode_ingest(args):
         torch.cuda.synchronize()
         ms = (time.perf_counter() - t0) / args.steps * 1000
         rows_after, fb = pipe.n_rows, sum(fallback) / total
+        merged = {"ingest_merged_index": pipe.ingest_merged_index,
+                  "ingest_merged_batch": pipe.ingest_merged_batch}
         counters = {k: round(getattr(pipe, k) / total, 1) for k in
                     ("recall_overflowed", "recall_rescanned", "recall_direct_fallbacks")}
         # per-stage timing outside the timed loop (the profiler synchronizes)
@@ -197,13 +214,50 @@ def mode_ingest(args):
                           "overflow": overflow, "ms_per_step": round(ms, 3),
                           "recall_ms_per_step": stages.get("recall"),
                           **{k + "_per_step": x for k, x in counters.items()},
-                          "rows_after": rows_after,
+                          "rows_after": rows_after, **merged,
                           "dropped": pipe.ingest_dropped, "index_rows": shard,
                           "batch": args.batch, "fallback_queries_per_step": round(fb, 1),
                           "stage_ms": stages}), flush=True)
         del pipe, ring, nxt, cur, out
         gc.collect()
         torch.cuda.empty_cache()
+
+
+def mode_dedup(args):
+    B, D, k, n = args.batch, args.dim, 16, 1_000_000
+    gen = torch.Generator(device="cuda").manual_seed(0)
+
+    def unit(*shape):
+        return torch.nn.functional.normalize(
+            torch.randn(*shape, generator=gen, device="cuda"), dim=-1)
+
+    X = unit(n, D).bfloat16()
+    ids = torch.randint(0, n, (B, k), generator=gen, device="cuda", dtype=torch.int32)
+    xowner = torch.randint(0, 64, (n,), generator=gen, device="cuda", dtype=torch.int32)
+    qowner = torch.randint(0, 64, (B,), generator=gen, device="cuda", dtype=torch.int32)
+    centres = unit(64, D)
+    which = torch.randint(0, 64, (B,), generator=gen, device="cuda")
+    rows = {"distinct": unit(B, D).bfloat16(),
+            "clustered": torch.nn.functional.normalize(
+                centres[which] + 0.15 * unit(B, D), dim=1).bfloat16(),
+            "identical": unit(1, D).bfloat16().expand(B, D).contiguous()}
+    elig = torch.ones(B, dtype=torch.bool, device="cuda")
+    for name, F in rows.items():
+        for owners in (False, True):
+            qo = qowner if owners else None
+            first = g.batch_first_similar(F, elig, 0.9, qo)
+            stored = int((first == torch.arange(B, device="cuda")).sum())
+            t = _time(lambda: g.batch_first_similar(F, elig, 0.9, qo), 30, reps=10)
+            print(json.dumps({"mode": "dedup", "op": "batch_first_similar", "rows": name,
+                              "owners": owners, "shape": [B, D], "stored": stored,
+                              **{k_: round(v, 4) for k_, v in t.items()}}), flush=True)
+    F = rows["distinct"]
+    for owners in (False, True):
+        own = dict(xowner=xowner, qowner=qowner) if owners else {}
+        t = _time(lambda: g.recall_dup_rows(F, ids, X, 0.9, **own), 30, reps=10)
+        print(json.dumps({"mode": "dedup", "op": "recall_dup_rows", "owners": owners,
+                          "shape": [B, k, D], "index_rows": n,
+                          **{k_: round(v, 4) for k_, v in t.items()}}), flush=True)
 
 
 def _realistic_salience(n, batch_rows=3750, seed=3):
@@ -330,7 +384,7 @@ def mode_forget(args):
 def main():
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("mode", choices=["quantize", "append", "ingest", "forget"])
+    ap.add_argument("mode", choices=["quantize", "append", "ingest", "forget", "dedup"])
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--dim", type=int, default=1024)
     ap.add_argument("--index", type=int, default=50_000_000)
@@ -340,13 +394,16 @@ def main():
     ap.add_argument("--overflow", default="direct",
                     help="ingest mode: PipelineConfig.recall_overflow, direct, rescan "
                          "or direct,rescan (alternating)")
+    ap.add_argument("--dedup", default="",
+                    help="ingest mode: comma list of PipelineConfig.ingest_dedup "
+                         "thresholds, each a variant beside plain ingest on")
     ap.add_argument("--content", default="synthetic,random",
                     help="ingest and forget modes: comma list of synthetic, random")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
     {"quantize": mode_quantize, "append": mode_append, "ingest": mode_ingest,
-     "forget": mode_forget}[args.mode](args)
+     "forget": mode_forget, "dedup": mode_dedup}[args.mode](args)
 
 
 if __name__ == "__main__":

@@ -486,6 +486,121 @@ def index_forget(
     return n_new
 
 
+# -- ingest dedup: near-duplicate detection (csrc/ingest_dedup.hip) ----------
+#
+# Similarity is the plain dot product of bf16 feature rows, which is what
+# recall scores: rows are not re-normalised, so two identical messages score
+# |f|^2, a few 1e-3 below 1. The kernels and the torch path accumulate in
+# fp32, the reference_* twins in fp64; they agree wherever no compared pair
+# lies within the fp32 accumulation error (about D * 2^-24) of tau.
+
+def _first_similar(S: torch.Tensor, elig: torch.Tensor, tau: float,
+                   owner: Optional[torch.Tensor]) -> torch.Tensor:
+    B = S.shape[0]
+    ar = torch.arange(B, device=S.device)
+    e = elig.bool()
+    ok = (S >= tau) & (ar.unsqueeze(0) < ar.unsqueeze(1)) & e.unsqueeze(1) & e.unsqueeze(0)
+    if owner is not None:
+        ok &= owner.unsqueeze(1) == owner.unsqueeze(0)
+    j = torch.where(ok, ar.unsqueeze(0), torch.full_like(ar, B).unsqueeze(0)).min(dim=1).values
+    first = torch.where(j < B, j, ar)
+    return torch.where(e, first, torch.full_like(first, -1)).to(torch.int32)
+
+
+def reference_batch_first_similar(F: torch.Tensor, elig: torch.Tensor, tau: float,
+                                  owner: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The batch rule of ingest dedup, dots in fp64: for an eligible row i,
+    first[i] is the smallest eligible j < i with owner[j] == owner[i] (when
+    owners are given) and dot(F_i, F_j) >= tau, or i itself if there is
+    none; first[i] = -1 for an ineligible i. Row i is stored iff first[i]
+    == i. Single link: a dropped row is within tau of an EARLIER ELIGIBLE
+    row, which may itself have been dropped."""
+    Fd = F.detach().cpu().double()
+    own = None if owner is None else owner.detach().cpu()
+    return _first_similar(Fd @ Fd.T, elig.detach().cpu(), float(tau), own)
+
+
+def batch_first_similar(F: torch.Tensor, elig: torch.Tensor, tau: float,
+                        owner: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """reference_batch_first_similar with fp32 accumulation, int32 [B]: one
+    launch of batch_first_similar_kernel (F . F^T over the lower triangle
+    on the bf16 MFMA, min j reduced in the block, one atomicMin per row and
+    block). F is bf16 [B, D], D % 32 == 0; elig bool [B]; owner int32 [B]
+    or None. CPU tensors take a torch path."""
+    B = F.shape[0]
+    if not F.is_cuda:
+        Ff = F.float()
+        return _first_similar(Ff @ Ff.T, elig, float(tau), owner)
+    elig = elig.bool().contiguous()
+    ar = torch.arange(B, dtype=torch.int32, device=F.device)
+    first = torch.where(elig, ar, torch.full_like(ar, -1))
+    if owner is not None:
+        owner = owner.to(torch.int32).contiguous()
+    ext().batch_first_similar(F.contiguous(), elig, float(tau), owner, first)
+    return first
+
+
+def _dup_rows(F: torch.Tensor, ids: torch.Tensor, X: torch.Tensor, tau: float,
+              xowner: Optional[torch.Tensor], qowner: Optional[torch.Tensor]
+              ) -> Tuple[torch.Tensor, torch.Tensor]:
+    B, n = F.shape[0], X.shape[0]
+    idl = ids.long()
+    if n == 0 or idl.shape[1] == 0:
+        return (torch.full((B,), -1, dtype=torch.int32, device=F.device),
+                torch.full((B,), -math.inf, dtype=F.dtype, device=F.device))
+    ok = (idl >= 0) & (idl < n)
+    safe = idl.clamp(0, n - 1)
+    dots = (X[safe] * F.unsqueeze(1)).sum(dim=2)
+    if xowner is not None:
+        ok &= xowner[safe] == qowner.unsqueeze(1)
+    dots = torch.where(ok & (dots >= tau), dots, torch.full_like(dots, -math.inf))
+    best = dots.max(dim=1).values
+    found = best > -math.inf
+    # equal dots go to the lowest id
+    tie = torch.where((dots == best.unsqueeze(1)) & found.unsqueeze(1), idl,
+                      torch.full_like(idl, n))
+    row = torch.where(found, tie.min(dim=1).values, torch.full_like(best, -1, dtype=torch.long))
+    return row.to(torch.int32), best
+
+
+def reference_recall_dup_rows(F: torch.Tensor, ids: torch.Tensor, X: torch.Tensor,
+                              tau: float, xowner: Optional[torch.Tensor] = None,
+                              qowner: Optional[torch.Tensor] = None
+                              ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The index rule of ingest dedup, dots in fp64: dup_row[i] is the row
+    among ids[i, :] with the largest dot(F_i, X_row) >= tau, equal dots
+    going to the lowest id, or -1. An id outside [0, len(X)) is skipped
+    (-1 = unfilled slot, stale, or another rank's row), and with owners so
+    is a row whose xowner differs from qowner[i]. dup_dot is that dot,
+    undefined where dup_row < 0. Only recalled rows are looked at."""
+    c = lambda t: None if t is None else t.detach().cpu()
+    return _dup_rows(F.detach().cpu().double(), ids.detach().cpu(),
+                     X.detach().cpu().double(), float(tau), c(xowner), c(qowner))
+
+
+def recall_dup_rows(F: torch.Tensor, ids: torch.Tensor, X: torch.Tensor, tau: float,
+                    xowner: Optional[torch.Tensor] = None,
+                    qowner: Optional[torch.Tensor] = None
+                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """reference_recall_dup_rows with fp32 accumulation, (int32 [B], fp32
+    [B]): one launch of recall_dup_rows_kernel (a wave per message, query
+    row in registers, candidates gathered with 16-byte loads). F bf16
+    [B, D], ids int [B, k], X bf16 [n, D], D % 8 == 0 and D <= 2048;
+    xowner int32 [n] and qowner int32 [B] go together. The kernel checks
+    every id against [0, n) before it loads through it. CPU tensors take a
+    torch path."""
+    if (xowner is None) != (qowner is None):
+        raise ValueError("recall_dup_rows: xowner and qowner go together")
+    if not F.is_cuda:
+        return _dup_rows(F.float(), ids, X.float(), float(tau), xowner, qowner)
+    if xowner is not None:
+        xowner = xowner.to(torch.int32).contiguous()
+        qowner = qowner.to(torch.int32).contiguous()
+    row, dot = ext().recall_dup_rows(F.contiguous(), ids.to(torch.int32).contiguous(),
+                                     X.contiguous(), float(tau), xowner, qowner)
+    return row, dot
+
+
 def topk_recall_fp8(Q8: torch.Tensor, X8: torch.Tensor, k: int, n_swaths: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """Stage-1 fp8 scan: candidate ids ranked by e4m3 cosine (csrc
     topk_recall_fp8_kernel). Inputs are uint8 views of e4m3 bytes."""

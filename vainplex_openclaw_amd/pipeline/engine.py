@@ -29,7 +29,10 @@ messages:
      that were not denied are appended to the live index shard — bf16 row,
      MXFP4 codes + scales, owner, salience — and later steps recall them;
      with ingest_full="evict" a full shard first forgets its lowest-
-     salience rows and is compacted in place (csrc/index_forget.hip)
+     salience rows and is compacted in place (csrc/index_forget.hip);
+     with ingest_dedup a message within the threshold of a recalled row
+     reinforces that row instead, and near-duplicates within the step are
+     stored once (csrc/ingest_dedup.hip)
 
 Multi-GPU (one process per GPU, torch.distributed over RCCL/xGMI):
 the index is sharded across ranks; recall queries are all-gathered so
@@ -122,6 +125,20 @@ class PipelineConfig:
     # (ops.gpu.topk_recall_threshold overflow=). threshold and
     # threshold_banded modes on the fp4 index.
     recall_overflow: str = "direct"
+    # near-duplicate consolidation at ingest: 0.0 = off (every kept message
+    # becomes a row); tau in (0, 1] = a kept message whose dot with one of
+    # its recalled rows is >= tau reinforces that row instead of being
+    # stored, and of several such messages in one step only the first is
+    # stored (FirewallPipeline._dedup states the rule). Needs ingest.
+    ingest_dedup: float = 0.0
+
+    def __post_init__(self):
+        if self.ingest_dedup != 0.0:
+            if not 0.0 < self.ingest_dedup <= 1.0:
+                raise ValueError(
+                    f"ingest_dedup must be 0.0 (off) or in (0, 1], not {self.ingest_dedup!r}")
+            if not self.ingest:
+                raise ValueError("ingest_dedup needs ingest=True")
 
 
 class StageProfiler:
@@ -214,6 +231,11 @@ class FirewallPipeline:
             # rows: recall_ids from before a forget name rows as they were
             self.forgotten = 0
             self.forget_epoch = 0
+            # ingest_dedup counters [merged into the index, merged within a
+            # batch], on the device: read through the properties only
+            self._merged = None
+            if cfg.ingest_dedup > 0.0:
+                self._merged = torch.zeros(2, dtype=torch.int64, device=self.device)
             cap = self.capacity
             self.index = torch.empty(cap, cfg.dim, dtype=torch.bfloat16, device=self.device)
             self.index[cfg.index_size:].zero_()
@@ -380,8 +402,75 @@ class FirewallPipeline:
         self.forget_epoch += 1
         return removed
 
+    @property
+    def ingest_merged_index(self) -> int:
+        """Kept messages, cumulative, that reinforced a recalled index row
+        instead of being stored (ingest_dedup). Reads the device counter."""
+        return 0 if self._merged is None else int(self._merged[0])
+
+    @property
+    def ingest_merged_batch(self) -> int:
+        """Kept messages, cumulative, dropped as near-duplicates of an
+        earlier message of their own step (ingest_dedup)."""
+        return 0 if self._merged is None else int(self._merged[1])
+
+    def _dedup(self, feats: torch.Tensor, keep: torch.Tensor, agent_idx: torch.Tensor,
+               recall_ids: torch.Tensor) -> torch.Tensor:
+        """The ingest_dedup rule for one step; returns the bool mask of the
+        messages to store. tau = cfg.ingest_dedup; similarity is the plain
+        dot of the bf16 feature rows, as recall scores it; with
+        recall_isolation only rows of the same agent can be duplicates.
+
+          1. keep[i] = verdict[i] != deny.
+          2. Index duplicates (g.recall_dup_rows): among message i's
+             recalled ids that are live rows of this rank's shard, the one
+             with the largest dot >= tau (equal dots: lowest id) is
+             dup_row[i], else -1. Only recalled rows are looked at: a copy
+             whose salience has decayed out of the weighted top-k is not
+             found and the message is stored afresh.
+          3. A kept message with dup_row[i] >= 0 is not stored;
+             salience[dup_row[i]] becomes 1.0, what the fresh copy would
+             have carried.
+          4. Batch duplicates (g.batch_first_similar) among elig = keep and
+             dup_row < 0: first[i] = the smallest eligible j < i with
+             dot >= tau, or i. Message i is stored iff first[i] == i. So no
+             two rows stored in one step are within tau of one another,
+             while a dropped row is within tau of an earlier eligible row,
+             not necessarily of a stored one (single link within a step).
+
+        Runs before any eviction of the step: a forget moves rows and
+        would make recall_ids stale. No host read; the two counters are
+        accumulated on the device."""
+        tau = self.cfg.ingest_dedup
+        n = self.n_rows
+        ids = recall_ids.to(torch.int32)
+        if self.world_size > 1:
+            # global ids keep the capacity stride; other shards' rows -> -1
+            base = self.rank * self.capacity
+            mine = (ids >= base) & (ids < base + self.capacity)
+            ids = torch.where(mine, ids - base, torch.full_like(ids, -1))
+        # a denied message merges with nothing
+        ids = torch.where(keep.unsqueeze(1), ids, torch.full_like(ids, -1))
+        qowner = xowner = None
+        if self.index_owner is not None:
+            qowner = agent_idx.to(torch.int32)
+            xowner = self.index_owner[:n]
+        dup_row, _ = g.recall_dup_rows(feats, ids, self.index[:n], tau,
+                                       xowner=xowner, qowner=qowner)
+        in_index = dup_row >= 0
+        # salience never exceeds 1.0, so max(s, 1.0) sets exactly 1.0; the
+        # messages without a duplicate contribute -inf to row 0: no change
+        self.salience.scatter_reduce_(
+            0, dup_row.clamp_min(0).long(),
+            torch.where(in_index, 1.0, -math.inf).to(self.salience.dtype), "amax")
+        elig = keep & ~in_index
+        first = g.batch_first_similar(feats, elig, tau, owner=qowner)
+        store = first == torch.arange(first.numel(), dtype=torch.int32, device=first.device)
+        self._merged += torch.stack([in_index.sum(), (elig & ~store).sum()])
+        return store
+
     def _ingest(self, feats: torch.Tensor, verdict: torch.Tensor,
-                agent_idx: torch.Tensor) -> None:
+                agent_idx: torch.Tensor, recall_ids: Optional[torch.Tensor] = None) -> None:
         """Remember this step's messages: append every feature row whose
         verdict is not deny to the live index (bf16 row, fp4 codes and
         scales, owner, salience 1.0) with one g.index_append launch. The
@@ -391,8 +480,13 @@ class FirewallPipeline:
         forgotten first, max(missing rows, evict_frac * capacity) of them;
         the step's recall and salience update are done by then, so its own
         results do not change, and only a step that keeps more messages
-        than the whole capacity still drops the excess."""
-        src = torch.nonzero(verdict != V_DENY).flatten().to(torch.int32)
+        than the whole capacity still drops the excess. With ingest_dedup
+        the rows to store are those _dedup leaves, found before any
+        eviction, and "kept" below counts them."""
+        keep = verdict != V_DENY
+        if self.cfg.ingest_dedup > 0.0:
+            keep = self._dedup(feats, keep, agent_idx, recall_ids)
+        src = torch.nonzero(keep).flatten().to(torch.int32)
         kept = int(src.numel())
         free = self.capacity - self.n_rows
         if self.cfg.ingest_full == "evict" and kept > free:
@@ -624,7 +718,7 @@ class FirewallPipeline:
 
         if cfg.ingest:
             prof.mark("ingest")
-            self._ingest(feats, verdict, agent_idx)
+            self._ingest(feats, verdict, agent_idx, recall_ids)
 
         prof.mark("end")
         self.batch_seq += 1
