@@ -101,6 +101,10 @@ __global__ void batch_first_similar_kernel(const __bf16*, const uint8_t*, const 
 __global__ void recall_dup_rows_kernel(const uint4*, const int32_t*, const uint4*,
                                        const int32_t*, const int32_t*, int, int, int, int,
                                        float, int32_t*, float*);
+__global__ void row_moments_kernel(const uint16_t*, int, float*, float*);
+__global__ void select_rescore_kernel(const float*, const int32_t*, const int32_t*,
+                                      const uint4*, const uint4*, const float*, int, int,
+                                      int, int, int, float*, int32_t*);
 struct AuditRecord64;
 __global__ void audit_pack_kernel(const int8_t*, const float*, const unsigned long long*,
                                   const unsigned long long*, const int32_t*, const float*,
@@ -178,13 +182,17 @@ torch::Tensor dfa_scan_multi(torch::Tensor bytes, torch::Tensor offsets,
   int n = offsets.numel() - 1;
   int n_dfas = meta.size(0);
   int n_families = family_ranges.size(0);
+  CHECK_CONTIG(bytes); CHECK_CONTIG(offsets); CHECK_CONTIG(meta); CHECK_CONTIG(family_ranges);
+  TORCH_CHECK(bytes.numel() <= INT32_MAX, "dfa_scan_multi: offsets are int32");
   auto hits = torch::zeros({n_families, n},
                            torch::dtype(torch::kInt64).device(bytes.device()));
-  int threads = 256;
+  if (n <= 0 || n_dfas <= 0) return hits;
+  TORCH_CHECK(n_dfas <= 65535, "dfa_scan_multi: too many sub-DFAs for grid.y");
+  // grid = messages x sub-DFAs; 128 = DFA_MULTI_THREADS (csrc/pattern_scan.hip):
+  // two-wave blocks spread the 1792 waves of a 4096-message batch over all CUs
+  int threads = 128;
   int blocks = (n + threads - 1) / threads;
-  size_t lds = (size_t)n_dfas * 256;
-  TORCH_CHECK(lds <= 160 * 1024, "class maps exceed LDS");
-  hipLaunchKernelGGL(dfa_scan_multi_kernel, dim3(blocks), dim3(threads), lds, cur_stream(),
+  hipLaunchKernelGGL(dfa_scan_multi_kernel, dim3(blocks, n_dfas), dim3(threads), 0, cur_stream(),
                      bytes.data_ptr<uint8_t>(), offsets.data_ptr<int32_t>(),
                      reinterpret_cast<const uint16_t*>(next_tab.data_ptr()),
                      reinterpret_cast<const unsigned long long*>(accept.data_ptr<int64_t>()),
@@ -192,7 +200,7 @@ torch::Tensor dfa_scan_multi(torch::Tensor bytes, torch::Tensor offsets,
                      class_maps.data_ptr<uint8_t>(), meta.data_ptr<int32_t>(),
                      family_ranges.data_ptr<int32_t>(), n_families,
                      reinterpret_cast<unsigned long long*>(hits.data_ptr<int64_t>()),
-                     n, n_dfas);
+                     n, (int)bytes.numel());
   return hits;
 }
 
@@ -924,6 +932,72 @@ std::vector<torch::Tensor> recall_dup_rows(torch::Tensor F, torch::Tensor ids,
   return {dup_row, dup_dot};
 }
 
+// csrc/recall_epilogue.hip: mean and correction=1 std of every row of a bf16
+// matrix, one pass, fp64 sums in a fixed order. Returns (mu, sigma) fp32 [nq].
+std::vector<torch::Tensor> row_moments(torch::Tensor S) {
+  CHECK_GPU(S); CHECK_CONTIG(S);
+  TORCH_CHECK(S.dtype() == torch::kBFloat16 && S.dim() == 2, "S must be bf16 [nq, m]");
+  long long nq = S.size(0), m = S.size(1);
+  TORCH_CHECK(m >= 1 && m < (1LL << 31) && nq < (1LL << 31), "row_moments: bad shape");
+  auto mu = torch::empty({nq}, torch::dtype(torch::kFloat32).device(S.device()));
+  auto sigma = torch::empty({nq}, torch::dtype(torch::kFloat32).device(S.device()));
+  if (nq == 0) return {mu, sigma};
+  hipLaunchKernelGGL(row_moments_kernel, dim3((unsigned)nq), dim3(256), 0, cur_stream(),
+                     reinterpret_cast<const uint16_t*>(S.data_ptr()), (int)m,
+                     mu.data_ptr<float>(), sigma.data_ptr<float>());
+  return {mu, sigma};
+}
+
+// csrc/recall_epilogue.hip: candidate select by scan score, exact fp32
+// rescore, salience weight and top-k, one block per query. The shapes it
+// takes are the ones ops.gpu.select_rescore routes here.
+std::vector<torch::Tensor> select_rescore(torch::Tensor cs, torch::Tensor ci,
+                                          torch::Tensor counts, torch::Tensor Q,
+                                          torch::Tensor X,
+                                          c10::optional<torch::Tensor> salience,
+                                          int64_t sel, int64_t k) {
+  CHECK_GPU(cs); CHECK_CONTIG(cs); CHECK_GPU(ci); CHECK_CONTIG(ci);
+  CHECK_GPU(counts); CHECK_CONTIG(counts);
+  CHECK_GPU(Q); CHECK_CONTIG(Q); CHECK_GPU(X); CHECK_CONTIG(X);
+  TORCH_CHECK(Q.dtype() == torch::kBFloat16 && Q.dim() == 2, "Q must be bf16 [nq, D]");
+  TORCH_CHECK(X.dtype() == torch::kBFloat16 && X.dim() == 2, "X must be bf16 [nx, D]");
+  long long nq = Q.size(0), nx = X.size(0);
+  int D = Q.size(1);
+  TORCH_CHECK(X.size(1) == D, "Q and X differ in D");
+  TORCH_CHECK(D > 0 && D % 8 == 0 && D <= 2048, "select_rescore needs D%8==0, D<=2048");
+  TORCH_CHECK(nq < (1LL << 31) && nx < (1LL << 31), "too many rows");
+  TORCH_CHECK(aligned16(Q) && aligned16(X), "Q and X must be 16-byte aligned");
+  TORCH_CHECK(cs.dtype() == torch::kFloat32 && cs.dim() == 2 && cs.size(0) == nq,
+              "cs must be fp32 [nq, cap]");
+  long long cap = cs.size(1);
+  TORCH_CHECK(ci.dtype() == torch::kInt32 && ci.dim() == 2 && ci.size(0) == nq &&
+              ci.size(1) == cap, "ci must be int32 [nq, cap]");
+  TORCH_CHECK(counts.dtype() == torch::kInt32 && counts.dim() == 1 && counts.numel() == nq,
+              "counts must be int32 [nq]");
+  TORCH_CHECK(cap >= 1 && cap <= 1024 && k >= 1 && k <= sel && sel <= cap,
+              "select_rescore needs 1 <= k <= sel <= cap <= 1024");
+  TORCH_CHECK(cs.device() == Q.device() && ci.device() == Q.device() &&
+              counts.device() == Q.device() && X.device() == Q.device(),
+              "select_rescore: tensors on different devices");
+  const float* sal = nullptr;
+  if (salience.has_value()) {
+    CHECK_GPU((*salience)); CHECK_CONTIG((*salience));
+    TORCH_CHECK(salience->dtype() == torch::kFloat32 && salience->dim() == 1 &&
+                salience->numel() >= nx && salience->device() == Q.device(),
+                "salience must be fp32 [>= nx] on Q's device");
+    sal = salience->data_ptr<float>();
+  }
+  auto out_s = torch::empty({nq, k}, torch::dtype(torch::kFloat32).device(Q.device()));
+  auto out_i = torch::empty({nq, k}, torch::dtype(torch::kInt32).device(Q.device()));
+  if (nq == 0) return {out_s, out_i};
+  hipLaunchKernelGGL(select_rescore_kernel, dim3((unsigned)nq), dim3(256), 0, cur_stream(),
+                     cs.data_ptr<float>(), ci.data_ptr<int32_t>(), counts.data_ptr<int32_t>(),
+                     reinterpret_cast<const uint4*>(Q.data_ptr()),
+                     reinterpret_cast<const uint4*>(X.data_ptr()), sal, (int)cap, (int)sel,
+                     (int)k, D, (int)nx, out_s.data_ptr<float>(), out_i.data_ptr<int32_t>());
+  return {out_s, out_i};
+}
+
 void register_host_envelope(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1051,6 +1125,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "ingest dedup: per message the recalled index row with the largest dot >= tau",
         py::arg("F"), py::arg("ids"), py::arg("X"), py::arg("tau"),
         py::arg("xowner") = c10::nullopt, py::arg("qowner") = c10::nullopt);
+  m.def("row_moments", &row_moments,
+        "per-row mean and correction=1 std of a bf16 matrix in one pass", py::arg("S"));
+  m.def("select_rescore", &select_rescore,
+        "threshold recall epilogue: select by scan score, exact rescore, salience, top-k",
+        py::arg("cs"), py::arg("ci"), py::arg("counts"), py::arg("Q"), py::arg("X"),
+        py::arg("salience") = c10::nullopt, py::arg("sel"), py::arg("k"));
   m.def("edit_distance", [](torch::Tensor bytes, torch::Tensor offsets) {
     // batched Levenshtein over string PAIRS: offsets has 2*n+1 entries;
     // pair i = strings (2i, 2i+1) in the packed byte buffer

@@ -24,6 +24,7 @@ SOURCES = [
     "csrc/fp4_quantize.hip",
     "csrc/index_forget.hip",
     "csrc/ingest_dedup.hip",
+    "csrc/recall_epilogue.hip",
     "csrc/firewall.hip",
     "csrc/edit_distance.hip",
     "csrc/fact_probe.hip",

@@ -859,6 +859,99 @@ def _scan_fp4x4_rescan(Q, Q4, QS, X4, theta, cap, x_norm_bound, owner, qowner, n
     return cs, ci, counts, n_over, n_rows
 
 
+def row_moments(S: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mean, correction=1 std) of every row of the bf16 GPU matrix S
+    [nq, m], fp32 [nq] each, in one pass over S (csrc row_moments_kernel:
+    fp64 sums shifted by the row's first element, fixed order). What
+    S.float().mean(1) and S.float().std(1) give, up to their own fp32
+    reduction error."""
+    mu, sigma = ext().row_moments(S.contiguous())
+    return mu, sigma
+
+
+def reference_select_rescore(
+    cs: torch.Tensor,
+    ci: torch.Tensor,
+    counts: torch.Tensor,
+    Q: torch.Tensor,
+    X: torch.Tensor,
+    salience: Optional[torch.Tensor],
+    sel: int,
+    k: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The recall epilogue in torch, device agnostic: the CPU path, the path
+    of the shapes select_rescore's kernel does not take, and the reference
+    of its tests. Inputs and outputs as select_rescore."""
+    cap = cs.shape[1]
+    # mask unfilled/overflowed slots
+    slot = torch.arange(cap, device=Q.device).unsqueeze(0)
+    valid = slot < counts.clamp_max(cap).unsqueeze(1)
+    cs = torch.where(valid, cs, torch.full_like(cs, -1e30))
+
+    # select: top candidates by scan score
+    top = torch.topk(cs, sel, dim=1)
+    ids = torch.gather(ci, 1, top.indices)
+
+    # exact fp32 rescore of the selected candidates (both dtypes: the
+    # bf16 scan's near-ties otherwise reorder the top-k at bf16 precision).
+    # salience (membrane semantics) folds into the rescore epilogue:
+    # final score = cosine * decayed salience, selection stays by raw
+    # cosine with overfetch (salience <= 1 so the weighted top-k is a
+    # subset of the higher-cosine candidates in the common case).
+    gidx = ids.long().clamp_min(0)
+    cand = X[gidx]  # [nq, sel, D]
+    exact = torch.einsum("qd,qkd->qk", Q.float(), cand.float())
+    if salience is not None:
+        exact = exact * salience[gidx]
+    exact = torch.where(ids < 0, torch.full_like(exact, -1e30), exact)
+    fin = torch.topk(exact, k, dim=1)
+    return fin.values, torch.gather(ids, 1, fin.indices)
+
+
+def select_rescore(
+    cs: torch.Tensor,
+    ci: torch.Tensor,
+    counts: torch.Tensor,
+    Q: torch.Tensor,
+    X: torch.Tensor,
+    salience: Optional[torch.Tensor],
+    sel: int,
+    k: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Epilogue of the threshold scans: from the candidate buffers cs / ci
+    [nq, cap] (fp32 scan scores, int32 row ids; unfilled slots -1e30 / -1)
+    and counts [nq] (hits per query, may exceed cap) to the final top-k.
+    Of the first min(counts, cap) slots the `sel` best by scan score are
+    rescored exactly, dot(Q row, X row) with fp32 sums over the bf16
+    values, times salience[id] if given, and the best k of those returned
+    as (scores fp32 [nq, k], sorted descending, ids int32 [nq, k]).
+    Positions past the valid candidates hold -1e30 / -1.
+
+    On the GPU this is one launch (csrc select_rescore_kernel) for bf16
+    Q / X with D % 8 == 0, D <= 2048, k <= sel <= cap <= 1024 and contiguous,
+    16-byte aligned tensors; there ties, at the `sel` boundary and in the
+    final order, go to the lower row id, so the result is the same from run
+    to run whatever order the scan filled the slots in. Every other shape,
+    and the CPU, takes reference_select_rescore (torch.topk's tie order)."""
+    D = Q.shape[1]
+    cap = cs.shape[1]
+    native = (
+        Q.is_cuda and Q.dtype == torch.bfloat16 and X.dtype == torch.bfloat16
+        and D % 8 == 0 and 0 < D <= 2048 and 1 <= k <= sel <= cap <= 1024
+        and cs.dtype == torch.float32 and ci.dtype == torch.int32
+        and counts.dtype == torch.int32
+        and (salience is None or (salience.dtype == torch.float32 and salience.dim() == 1
+                                  and salience.is_contiguous()
+                                  and salience.numel() >= X.shape[0]))
+        and all(t.is_contiguous() for t in (cs, ci, counts, Q, X))
+        and Q.data_ptr() % 16 == 0 and X.data_ptr() % 16 == 0
+    )
+    if not native:
+        return reference_select_rescore(cs, ci, counts, Q, X, salience, sel, k)
+    s, i = ext().select_rescore(cs, ci, counts, Q, X, salience, sel, k)
+    return s, i
+
+
 def topk_recall_threshold(
     Q: torch.Tensor,
     X: torch.Tensor,
@@ -930,10 +1023,16 @@ def topk_recall_threshold(
         raise NotImplementedError(
             "overflow='rescan': fp4x4 scan (q4, D <= 1024) only")
 
-    # 1. per-query score statistics from a sample (bf16 matmul)
-    sample = torch.matmul(Q, X[:m].T).float()  # [nq, m]
-    mu = sample.mean(dim=1)
-    sigma = sample.std(dim=1).clamp_min(1e-6)
+    # 1. per-query score statistics from a sample (bf16 matmul); on the GPU
+    # both moments come from one pass over the bf16 scores (row_moments)
+    sample = torch.matmul(Q, X[:m].T)  # [nq, m]
+    if sample.is_cuda and sample.dtype == torch.bfloat16 and m >= 2:
+        mu, sigma = row_moments(sample)
+    else:
+        sample = sample.float()
+        mu = sample.mean(dim=1)
+        sigma = sample.std(dim=1)
+    sigma = sigma.clamp_min(1e-6)
     # Gaussian tail: P(score > theta) = C/nx
     p = min(0.5, max(target_candidates / max(nx, 1), 1e-12))
     try:
@@ -1004,37 +1103,15 @@ def topk_recall_threshold(
         cs, ci, counts = ext().topk_scan_threshold(
             Q, X, theta, cap, 0, False, False, xowner=owner, qowner=qowner)
 
-    # 3. mask unfilled/overflowed slots
-    slot = torch.arange(cap, device=Q.device).unsqueeze(0)
-    valid = slot < counts.clamp_max(cap).unsqueeze(1)
-    cs = torch.where(valid, cs, torch.full_like(cs, -1e30))
-
-    # 4. select: top candidates by scan score (wider for the noisier
+    # 3.-4. select the top candidates by scan score (wider for the noisier
     # fp4 scan, and for salience weighting — the weighted top-k can sit
     # below the raw-cosine top-2k; the exact rescore makes overfetch
-    # nearly free)
+    # nearly free), rescore them exactly and keep the top k
     if use_fp4 or salience is not None:
         sel = min(cap, max(8 * k if salience is not None else 4 * k, 128))
     else:
         sel = min(cap, max(2 * k, 32))
-    top = torch.topk(cs, sel, dim=1)
-    ids = torch.gather(ci, 1, top.indices)
-
-    # exact fp32 rescore of the selected candidates (both dtypes: the
-    # bf16 scan's near-ties otherwise reorder the top-k at bf16 precision).
-    # salience (membrane semantics) folds into the rescore epilogue:
-    # final score = cosine * decayed salience, selection stays by raw
-    # cosine with overfetch (salience <= 1 so the weighted top-k is a
-    # subset of the higher-cosine candidates in the common case).
-    gidx = ids.long().clamp_min(0)
-    cand = X[gidx]  # [nq, sel, D]
-    exact = torch.einsum("qd,qkd->qk", Q.float(), cand.float())
-    if salience is not None:
-        exact = exact * salience[gidx]
-    exact = torch.where(ids < 0, torch.full_like(exact, -1e30), exact)
-    fin = torch.topk(exact, k, dim=1)
-    out_s = fin.values
-    out_i = torch.gather(ids, 1, fin.indices)
+    out_s, out_i = select_rescore(cs, ci, counts, Q, X, salience, sel, k)
 
     # 5. fallback for underflowed queries (non-Gaussian tails / theta high)
     if owner is None:
