@@ -93,9 +93,13 @@ __global__ void fact_probe_kernel(const uint8_t*, const int32_t*,
                                   int, int32_t*, int32_t*, int);
 __global__ void fp4_quantize_append_kernel(const uint16_t*, const int32_t*, int, long long,
                                            int, long long, uint16_t*, uint8_t*, uint8_t*,
-                                           int32_t*, const int32_t*, float*, float);
+                                           int32_t*, const int32_t*, float*, float,
+                                           long long*, long long);
 __global__ void index_move_rows_kernel(const int32_t*, const int32_t*, long long, int, int,
-                                       uint4*, uint4*, uint32_t*, uint32_t*, uint32_t*);
+                                       uint4*, uint4*, uint32_t*, uint32_t*, uint32_t*,
+                                       uint2*);
+__global__ void index_find_ids_kernel(const long long*, long long, const long long*, int,
+                                      int32_t*);
 __global__ void batch_first_similar_kernel(const __bf16*, const uint8_t*, const int32_t*,
                                            int, int, float, int32_t*);
 __global__ void recall_dup_rows_kernel(const uint4*, const int32_t*, const uint4*,
@@ -663,7 +667,8 @@ static bool aligned16(const torch::Tensor& t) {
 static void launch_fp4_quantize_append(
     const torch::Tensor& feats, const int32_t* src_idx, long long n, long long dst_row0,
     uint16_t* index_dst, uint8_t* x4, uint8_t* xs, int32_t* owner_dst,
-    const int32_t* owner_src, float* salience_dst, float salience_init) {
+    const int32_t* owner_src, float* salience_dst, float salience_init,
+    long long* id_dst = nullptr, long long id_base = 0) {
   if (n == 0) return;
   int D = feats.size(1);
   long long items = n * (D / 16);
@@ -674,7 +679,7 @@ static void launch_fp4_quantize_append(
                      cur_stream(),
                      reinterpret_cast<const uint16_t*>(feats.data_ptr()), src_idx,
                      (int)feats.size(0), n, D, dst_row0, index_dst, x4, xs, owner_dst,
-                     owner_src, salience_dst, salience_init);
+                     owner_src, salience_dst, salience_init, id_dst, id_base);
 }
 
 static void check_fp4_dst(const torch::Tensor& X4, const torch::Tensor& XS, long long rows,
@@ -715,9 +720,11 @@ void index_append(torch::Tensor feats, c10::optional<torch::Tensor> src_idx,
                   c10::optional<torch::Tensor> X4, c10::optional<torch::Tensor> XS,
                   c10::optional<torch::Tensor> owner_dst,
                   c10::optional<torch::Tensor> owner_src,
-                  c10::optional<torch::Tensor> salience_dst, double salience_init) {
+                  c10::optional<torch::Tensor> salience_dst, double salience_init,
+                  c10::optional<torch::Tensor> id_dst, int64_t id_base) {
   // rows dst_row0 + i of the live index <- feats[src_idx[i]] (or feats[i]):
-  // bf16 copy, fp4 codes + scales, owner and salience in one launch
+  // bf16 copy, fp4 codes + scales, owner, salience and memory id
+  // (id_base + the source row) in one launch
   CHECK_GPU(feats); CHECK_CONTIG(feats); CHECK_GPU(index); CHECK_CONTIG(index);
   TORCH_CHECK(feats.dtype() == torch::kBFloat16 && feats.dim() == 2,
               "feats must be bf16 [m, D]");
@@ -768,9 +775,17 @@ void index_append(torch::Tensor feats, c10::optional<torch::Tensor> src_idx,
                 salience_dst->numel() == cap, "salience_dst must be f32 [cap]");
     sdp = salience_dst->data_ptr<float>();
   }
+  long long* idp = nullptr;
+  if (id_dst.has_value()) {
+    CHECK_GPU((*id_dst)); CHECK_CONTIG((*id_dst));
+    TORCH_CHECK(id_dst->dtype() == torch::kInt64 && id_dst->dim() == 1 &&
+                id_dst->numel() == cap, "id_dst must be int64 [cap]");
+    TORCH_CHECK(id_dst->device() == index.device(), "id_dst and index on different devices");
+    idp = reinterpret_cast<long long*>(id_dst->data_ptr<int64_t>());
+  }
   launch_fp4_quantize_append(feats, sp, n, dst_row0,
                              reinterpret_cast<uint16_t*>(index.data_ptr()), x4p, xsp, odp,
-                             osp, sdp, (float)salience_init);
+                             osp, sdp, (float)salience_init, idp, (long long)id_base);
 }
 
 // -- forgetting: in-place row moves (csrc/index_forget.hip) ----------------
@@ -779,7 +794,8 @@ void index_move_rows(torch::Tensor src, torch::Tensor dst,
                      c10::optional<torch::Tensor> index,
                      c10::optional<torch::Tensor> X4, c10::optional<torch::Tensor> XS,
                      c10::optional<torch::Tensor> owner,
-                     c10::optional<torch::Tensor> salience) {
+                     c10::optional<torch::Tensor> salience,
+                     c10::optional<torch::Tensor> ids) {
   // row dst[j] of every given buffer <- row src[j], bitwise, in one launch;
   // a pair with an index outside [0, cap) is skipped by the kernel
   CHECK_GPU(src); CHECK_CONTIG(src); CHECK_GPU(dst); CHECK_CONTIG(dst);
@@ -788,7 +804,8 @@ void index_move_rows(torch::Tensor src, torch::Tensor dst,
   TORCH_CHECK(src.numel() == dst.numel(), "src and dst differ in length");
   TORCH_CHECK(src.device() == dst.device(), "src and dst on different devices");
   TORCH_CHECK(index.has_value() || X4.has_value() || owner.has_value() ||
-              salience.has_value(), "index_move_rows needs at least one buffer");
+              salience.has_value() || ids.has_value(),
+              "index_move_rows needs at least one buffer");
   TORCH_CHECK(X4.has_value() == XS.has_value(), "X4 and XS go together");
   long long cap = -1;
   int D = 0;
@@ -836,6 +853,13 @@ void index_move_rows(torch::Tensor src, torch::Tensor dst,
     same_cap(*salience, "salience");
     sp = reinterpret_cast<uint32_t*>(salience->data_ptr());
   }
+  uint2* idp = nullptr;
+  if (ids.has_value()) {
+    CHECK_GPU((*ids)); CHECK_CONTIG((*ids));
+    TORCH_CHECK(ids->dtype() == torch::kInt64 && ids->dim() == 1, "ids must be int64 [cap]");
+    same_cap(*ids, "ids");
+    idp = reinterpret_cast<uint2*>(ids->data_ptr());
+  }
   TORCH_CHECK(cap < (1LL << 31), "index has too many rows");
   long long m = src.numel();
   if (m == 0) return;
@@ -845,7 +869,34 @@ void index_move_rows(torch::Tensor src, torch::Tensor dst,
   if (blocks > 256 * 8) blocks = 256 * 8;
   hipLaunchKernelGGL(index_move_rows_kernel, dim3((unsigned)blocks), dim3(256), 0,
                      cur_stream(), src.data_ptr<int32_t>(), dst.data_ptr<int32_t>(), m,
-                     (int)cap, D, ip, x4p, xsp, op, sp);
+                     (int)cap, D, ip, x4p, xsp, op, sp, idp);
+}
+
+// -- memory ids: rows by id (csrc/index_ids.hip) ----------------------------
+
+void index_find_ids(torch::Tensor col, torch::Tensor want, torch::Tensor row_out) {
+  // row_out[j] <- max(row_out[j], highest row of col holding want[j]); want
+  // is one chunk, ascending and distinct; the caller prefills row_out with -1
+  CHECK_GPU(col); CHECK_CONTIG(col); CHECK_GPU(want); CHECK_CONTIG(want);
+  CHECK_GPU(row_out); CHECK_CONTIG(row_out);
+  TORCH_CHECK(col.dtype() == torch::kInt64 && col.dim() == 1, "col must be int64 [n]");
+  TORCH_CHECK(want.dtype() == torch::kInt64 && want.dim() == 1, "want must be int64 [m]");
+  TORCH_CHECK(row_out.dtype() == torch::kInt32 && row_out.dim() == 1 &&
+              row_out.numel() == want.numel(), "row_out must be int32 [m]");
+  TORCH_CHECK(col.device() == want.device() && col.device() == row_out.device(),
+              "col, want and row_out on different devices");
+  long long n = col.numel(), m = want.numel();
+  TORCH_CHECK(n < (1LL << 31), "col has too many rows");
+  TORCH_CHECK(m <= 4096, "want holds more than one chunk (4096 ids)");
+  if (n == 0 || m == 0) return;
+  // one 16-byte pair per lane; 32 KB of LDS a block, so 4 blocks a CU at most
+  long long blocks = (n / 2 + 255) / 256;
+  if (blocks < 1) blocks = 1;
+  if (blocks > 256 * 4) blocks = 256 * 4;
+  hipLaunchKernelGGL(index_find_ids_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                     cur_stream(), reinterpret_cast<const long long*>(col.data_ptr<int64_t>()),
+                     n, reinterpret_cast<const long long*>(want.data_ptr<int64_t>()), (int)m,
+                     row_out.data_ptr<int32_t>());
 }
 
 // -- ingest dedup: near-duplicate detection (csrc/ingest_dedup.hip) --------
@@ -1112,12 +1163,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("feats"), py::arg("src_idx"), py::arg("dst_row0"), py::arg("index"),
         py::arg("X4") = c10::nullopt, py::arg("XS") = c10::nullopt,
         py::arg("owner_dst") = c10::nullopt, py::arg("owner_src") = c10::nullopt,
-        py::arg("salience_dst") = c10::nullopt, py::arg("salience_init") = 1.0);
+        py::arg("salience_dst") = c10::nullopt, py::arg("salience_init") = 1.0,
+        py::arg("id_dst") = c10::nullopt, py::arg("id_base") = 0);
   m.def("index_move_rows", &index_move_rows,
         "move rows src[j] onto rows dst[j] of the live recall index buffers, in place",
         py::arg("src"), py::arg("dst"), py::arg("index") = c10::nullopt,
         py::arg("X4") = c10::nullopt, py::arg("XS") = c10::nullopt,
-        py::arg("owner") = c10::nullopt, py::arg("salience") = c10::nullopt);
+        py::arg("owner") = c10::nullopt, py::arg("salience") = c10::nullopt,
+        py::arg("ids") = c10::nullopt);
+  m.def("index_find_ids", &index_find_ids,
+        "rows of an id column holding each id of one sorted, distinct chunk (atomicMax)",
+        py::arg("col"), py::arg("want"), py::arg("row_out"));
   m.def("batch_first_similar", &batch_first_similar,
         "ingest dedup: lower first[i] to the earliest similar eligible row j < i",
         py::arg("F"), py::arg("elig"), py::arg("tau"), py::arg("owner"), py::arg("first"));

@@ -4,7 +4,8 @@
 //   - the packed e2m1 nibbles in the hardware fragment order of the fp4
 //     scan's B operand (ops.gpu.fp4_perm128), X4 [*, D/2]
 //   - the e8m0 group scales, XS [*, D/32]
-//   - optionally the bf16 copy, the owner id and the initial salience
+//   - optionally the bf16 copy, the owner id, the initial salience and the
+//     row's stable memory id (id_base + the batch position it came from)
 // The output is bit-for-bit ops.gpu.to_fp4_mx (the torch oracle) on finite
 // input; ops.gpu.fp4_mx_spec states the same integer rule in Python.
 //
@@ -39,7 +40,9 @@ void fp4_quantize_append_kernel(
     int32_t* __restrict__ owner_dst,       // [cap] or null
     const int32_t* __restrict__ owner_src, // [m] (with owner_dst)
     float* __restrict__ salience_dst,      // [cap] or null
-    float salience_init) {
+    float salience_init,
+    long long* __restrict__ id_dst,        // int64 [cap] or null
+    long long id_base) {
   const int lpr = D >> 4;  // lanes per row
   const long long items = n * lpr;
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -76,6 +79,7 @@ void fp4_quantize_append_kernel(
     if (ok && h == 0) {
       if (owner_dst != nullptr) owner_dst[dst] = owner_src[src];
       if (salience_dst != nullptr) salience_dst[dst] = salience_init;
+      if (id_dst != nullptr) id_dst[dst] = id_base + src;
     }
     if (X4 == nullptr) continue;  // uniform
 

@@ -15,6 +15,7 @@
 //   - the fp4 codes X4     [cap, D/2]   D/2 bytes   uint4 per lane
 //   - the e8m0 scales XS   [cap, D/32]  D/32 bytes  dwords (4 B at D = 128)
 //   - owner (int32) and salience (fp32) [cap]       one dword each
+//   - the memory ids (int64) [cap]                  one 8-byte word
 // X4/XS have the row layout fp4_quantize_append_kernel writes: codes and
 // scales are row-major per row, so a move is a byte copy. Copies are
 // bitwise; every byte outside the rows named in dst stays as it is.
@@ -42,7 +43,8 @@ void index_move_rows_kernel(
     uint4* X4,           // [cap, D/2] or null
     uint32_t* XS,        // [cap, D/32] or null (with X4)
     uint32_t* owner,     // int32 bits [cap] or null
-    uint32_t* salience)  // fp32 bits [cap] or null
+    uint32_t* salience,  // fp32 bits [cap] or null
+    uint2* ids)          // int64 bits [cap] or null
 {
   const int lane = threadIdx.x & 63;
   const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -59,6 +61,7 @@ void index_move_rows_kernel(
     // the short rows first: their loads stay in flight over the bf16 row
     uint4 code = make_uint4(0, 0, 0, 0);
     uint32_t scale = 0, own = 0, sal = 0;
+    uint2 id = make_uint2(0, 0);
     if (X4 != nullptr) {
       if (lane < code_q) code = X4[(long long)s * code_q + lane];
       if (lane < scale_w) scale = XS[(long long)s * scale_w + lane];
@@ -66,6 +69,7 @@ void index_move_rows_kernel(
     if (lane == 0) {
       if (owner != nullptr) own = owner[s];
       if (salience != nullptr) sal = salience[s];
+      if (ids != nullptr) id = ids[s];
     }
 
     if (index != nullptr) {
@@ -92,6 +96,7 @@ void index_move_rows_kernel(
     if (lane == 0) {
       if (owner != nullptr) owner[d] = own;
       if (salience != nullptr) salience[d] = sal;
+      if (ids != nullptr) ids[d] = id;
     }
   }
 }

@@ -23,6 +23,7 @@ SOURCES = [
     "csrc/topk_recall.hip",
     "csrc/fp4_quantize.hip",
     "csrc/index_forget.hip",
+    "csrc/index_ids.hip",
     "csrc/ingest_dedup.hip",
     "csrc/recall_epilogue.hip",
     "csrc/firewall.hip",

@@ -30,6 +30,10 @@
              ingest on (the yardstick) in every round; every line carries
              ingest_merged_index / ingest_merged_batch, rows_after and the
              overflow counters. Results: profiles/README.md, "ingest dedup".
+             --memory-ids runs, per round, plain ingest on, ingest on with
+             PipelineConfig.memory_ids, and plain ingest on again: the
+             first two are the pair, the two plain runs the spread.
+             Results: profiles/README.md, "memory ids and snapshots".
   dedup      the two ingest-dedup kernels (csrc/ingest_dedup.hip) alone at
              the per-step shape (--batch x --dim, k = 16 recalled ids into a
              1M-row index): ms, hipEvent timed, on rows without duplicates,
@@ -45,6 +49,16 @@
              step's ms against the median plain step, per kind of content
              (--content). Results live in profiles/README.md, section
              "index forget".
+  find       find_rows (csrc/index_ids.hip) against reference_find_rows
+             (torch sort + searchsorted) on a column of --index distinct ids
+             (50M) for 1, 4096 and 65 536 wanted ids, half of them present:
+             wall ms around a device synchronise and the peak of
+             torch.cuda.max_memory_allocated over what was allocated before
+             the call, the two paths alternating.
+  snapshot   FirewallPipeline.save_memory / load_memory at --index x --dim
+             (1M x 1024 is the recorded shape), memory_ids and
+             recall_isolation on: wall seconds and bytes written, to a
+             temporary directory that is removed afterwards.
 
 Every mode needs a GPU and prints one JSON line per measurement.
 """
@@ -175,6 +189,8 @@ def mode_ingest(args):
     if taus:
         # against plain ingest on, the parent's step, in the same round
         ingest_variants = ("on",) + tuple(f"on+dedup={t}" for t in taus)
+    if args.memory_ids:
+        ingest_variants = ("on", "on+ids", "on")
     variants = [(c, v, m) for _ in range(args.rounds) for c in args.content.split(",")
                 for v in ingest_variants for m in modes]
     for content, v, overflow in variants:
@@ -184,6 +200,7 @@ def mode_ingest(args):
                              ingest=v.startswith("on"),
                              ingest_capacity=(total + 3) * args.batch,
                              ingest_dedup=float(v.partition("=")[2] or 0.0),
+                             memory_ids=v.endswith("+ids"),
                              recall_overflow=overflow)
         pipe = FirewallPipeline(cfg, device="cuda:0")
         ring = StagingRing(pipe, max_bytes=8 << 20, max_msgs=max(args.batch, 8192) + 1)
@@ -381,10 +398,78 @@ def mode_forget(args):
         torch.cuda.empty_cache()
 
 
+def mode_find(args):
+    n = args.index
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    # distinct ids in no order: even numbers, so that odd ones are absent
+    col = torch.randperm(n, generator=gen, device="cuda") * 2 + (1 << 48)
+    paths = (("find_rows", g.find_rows), ("reference_find_rows", g.reference_find_rows))
+    for m in (1, 4096, 65536):
+        pick = col[torch.randint(0, n, (m,), generator=gen, device="cuda")]
+        want = pick + (torch.arange(m, device="cuda") & 1)  # every other one absent
+        outs = {}
+        for rnd in range(-1, args.rounds):  # round -1 warms both paths up
+            for name, fn in paths:
+                gc.collect()
+                torch.cuda.empty_cache()
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                before = torch.cuda.memory_allocated()
+                t0 = time.perf_counter()
+                out = fn(col, want)
+                torch.cuda.synchronize()
+                ms = (time.perf_counter() - t0) * 1000
+                peak = torch.cuda.max_memory_allocated() - before
+                outs[name] = out
+                if rnd < 0:
+                    continue
+                print(json.dumps({"mode": "find", "op": name, "rows": n, "wanted": m,
+                                  "round": rnd, "ms": round(ms, 3),
+                                  "peak_extra_MB": round(peak / 1e6, 2),
+                                  "found": int((out >= 0).sum())}), flush=True)
+        print(json.dumps({"mode": "find", "wanted": m, "paths_equal": bool(
+            torch.equal(outs["find_rows"], outs["reference_find_rows"]))}), flush=True)
+        del outs, out
+
+
+def mode_snapshot(args):
+    import shutil
+    import tempfile
+
+    from vainplex_openclaw_amd.pipeline.engine import FirewallPipeline, PipelineConfig
+
+    cfg = PipelineConfig(batch=args.batch, dim=args.dim, index_size=args.index,
+                         recall_isolation=True, memory_ids=True, ingest=True,
+                         ingest_capacity=args.batch)
+    pipe = FirewallPipeline(cfg, device="cuda:0")
+    other = FirewallPipeline(cfg, device="cuda:0")
+    root = tempfile.mkdtemp(prefix="memory-snapshot-")
+    try:
+        for rnd in range(args.rounds):
+            path = os.path.join(root, f"snap{rnd}")
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            man = pipe.save_memory(path)
+            t1 = time.perf_counter()
+            other.load_memory(path)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            same = bool(torch.equal(other.index4[0][:pipe.n_rows], pipe.index4[0][:pipe.n_rows])
+                        and torch.equal(other.index_ids, pipe.index_ids))
+            print(json.dumps({"mode": "snapshot", "rows": pipe.n_rows, "dim": args.dim,
+                              "round": rnd, "bytes": sum(man["files"].values()),
+                              "save_s": round(t1 - t0, 3), "load_s": round(t2 - t1, 3),
+                              "restored_equal": same}), flush=True)
+            shutil.rmtree(path)
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("mode", choices=["quantize", "append", "ingest", "forget", "dedup"])
+    ap.add_argument("mode", choices=["quantize", "append", "ingest", "forget", "dedup",
+                                     "find", "snapshot"])
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--dim", type=int, default=1024)
     ap.add_argument("--index", type=int, default=50_000_000)
@@ -397,13 +482,17 @@ def main():
     ap.add_argument("--dedup", default="",
                     help="ingest mode: comma list of PipelineConfig.ingest_dedup "
                          "thresholds, each a variant beside plain ingest on")
+    ap.add_argument("--memory-ids", action="store_true",
+                    help="ingest mode: plain ingest on, ingest on with memory ids, plain "
+                         "ingest on again, per round")
     ap.add_argument("--content", default="synthetic,random",
                     help="ingest and forget modes: comma list of synthetic, random")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU")
     {"quantize": mode_quantize, "append": mode_append, "ingest": mode_ingest,
-     "forget": mode_forget, "dedup": mode_dedup}[args.mode](args)
+     "forget": mode_forget, "dedup": mode_dedup, "find": mode_find,
+     "snapshot": mode_snapshot}[args.mode](args)
 
 
 if __name__ == "__main__":

@@ -383,16 +383,25 @@ def index_append(
     owner_src: Optional[torch.Tensor] = None,
     salience_dst: Optional[torch.Tensor] = None,
     salience_init: float = 1.0,
+    id_dst: Optional[torch.Tensor] = None,
+    id_base: int = 0,
 ) -> None:
     """Append rows to a live recall index in one launch: row dst_row0 + i
     of `index` (bf16 [cap, D]), of the MXFP4 pair X4/XS, of `owner_dst`
     and of `salience_dst` receives feats[src_idx[i]] (feats[i] when
     src_idx is None), its fp4 codes and scales (as to_fp4_mx would build
-    them), owner_src[src_idx[i]] and salience_init. Every destination
-    except `index` is optional. A src_idx entry outside feats leaves its
-    destination row untouched; dst_row0 + n past the capacity raises."""
-    ext().index_append(feats, src_idx, int(dst_row0), index, X4, XS,
-                       owner_dst, owner_src, salience_dst, float(salience_init))
+    them), owner_src[src_idx[i]] and salience_init; row dst_row0 + i of
+    `id_dst` (int64 [cap]) receives id_base + src_idx[i], the row's memory
+    id. Every destination except `index` is optional. A src_idx entry
+    outside feats leaves its destination row untouched; dst_row0 + n past
+    the capacity raises."""
+    if id_dst is None:
+        ext().index_append(feats, src_idx, int(dst_row0), index, X4, XS,
+                           owner_dst, owner_src, salience_dst, float(salience_init))
+    else:
+        ext().index_append(feats, src_idx, int(dst_row0), index, X4, XS,
+                           owner_dst, owner_src, salience_dst, float(salience_init),
+                           id_dst, int(id_base))
 
 
 def evict_mask(salience: torch.Tensor, count: int) -> torch.Tensor:
@@ -447,22 +456,23 @@ def index_move_rows(
     XS: Optional[torch.Tensor] = None,
     owner: Optional[torch.Tensor] = None,
     salience: Optional[torch.Tensor] = None,
+    ids: Optional[torch.Tensor] = None,
 ) -> None:
     """Row dst[j] of every given buffer takes the contents of row src[j],
     bitwise and in place, in one launch (csrc/index_forget.hip). `index`
     is bf16 [cap, D], X4/XS the MXFP4 pair, owner int32 [cap], salience
-    fp32 [cap]; any subset, at least one. dst must be unique and disjoint
+    fp32 [cap], ids int64 [cap]; any subset, at least one. dst must be unique and disjoint
     from src (forget_plan's lists are). The kernel skips a pair with an
     index outside [0, cap). CPU tensors, and a bf16 row that is not a
     multiple of 16 bytes (D % 8 != 0), take torch indexing instead."""
-    bufs = [b for b in (index, X4, XS, owner, salience) if b is not None]
+    bufs = [b for b in (index, X4, XS, owner, salience, ids) if b is not None]
     if not bufs:
         raise ValueError("index_move_rows needs at least one buffer")
     if src.numel() == 0:
         return
     on_gpu = src.is_cuda and all(b.is_cuda for b in bufs)
     if on_gpu and (index is None or index.shape[1] % 8 == 0):
-        ext().index_move_rows(src, dst, index, X4, XS, owner, salience)
+        ext().index_move_rows(src, dst, index, X4, XS, owner, salience, ids)
         return
     s, d = src.long(), dst.long()
     for b in bufs:
@@ -476,14 +486,65 @@ def index_forget(
     XS: Optional[torch.Tensor] = None,
     owner: Optional[torch.Tensor] = None,
     salience: Optional[torch.Tensor] = None,
+    ids: Optional[torch.Tensor] = None,
 ) -> int:
     """Forget the live rows marked in `dead` (bool[n], n = live rows):
     forget_plan, then one index_move_rows over the given buffers. Returns
     n_new; the live rows are then [:n_new] of every buffer and the
     contents of rows >= n_new are unspecified."""
     n_new, dst, src = forget_plan(dead)
-    index_move_rows(src, dst, index=index, X4=X4, XS=XS, owner=owner, salience=salience)
+    index_move_rows(src, dst, index=index, X4=X4, XS=XS, owner=owner, salience=salience,
+                    ids=ids)
     return n_new
+
+
+# -- memory ids: rows by id (csrc/index_ids.hip) -----------------------------
+
+FIND_CHUNK = 4096  # wanted ids per launch: 32 KB of LDS
+
+
+def reference_find_rows(ids_col: torch.Tensor, want: torch.Tensor) -> torch.Tensor:
+    """The rule of find_rows in torch, on any device: int32 [len(want)],
+    the row of `ids_col` (int64 [n], the live prefix of the ids column)
+    holding each wanted id, or -1. A negative id is never found, on either
+    side; of several rows holding one id the highest wins. A stable sort
+    keeps equal ids in row order, so the last of a run (searchsorted
+    right=True, minus one) is the highest row."""
+    want = want.to(torch.int64)
+    out = torch.full((want.numel(),), -1, dtype=torch.int32, device=ids_col.device)
+    if ids_col.numel() == 0 or want.numel() == 0:
+        return out
+    vals, order = torch.sort(ids_col, stable=True)
+    pos = torch.searchsorted(vals, want, right=True) - 1
+    posc = pos.clamp_min(0)
+    hit = (pos >= 0) & (vals[posc] == want) & (want >= 0)
+    return torch.where(hit, order[posc].to(torch.int32), out)
+
+
+def find_rows(ids_col: torch.Tensor, want: torch.Tensor) -> torch.Tensor:
+    """int32 [len(want)]: the row of `ids_col` (int64 [n], the live prefix
+    index_ids[:n_rows]) that holds each wanted id, -1 where none does.
+    `want` is int64 in any order and may repeat ids; negative ids are never
+    found; of several rows holding one id the highest wins
+    (reference_find_rows is the same rule in torch, and the CPU path).
+
+    One pass over the column per FIND_CHUNK wanted ids
+    (csrc/index_ids.hip): the sorted, distinct ids of a chunk sit in LDS and
+    every row is searched there, so nothing of the column's size is
+    allocated. torch.unique sizes its result on the host; that is the one
+    host read."""
+    if not ids_col.is_cuda:
+        return reference_find_rows(ids_col, want)
+    want = want.to(device=ids_col.device, dtype=torch.int64).contiguous()
+    m = want.numel()
+    if ids_col.numel() == 0 or m == 0:
+        return torch.full((m,), -1, dtype=torch.int32, device=ids_col.device)
+    uniq, inv = torch.unique(want, return_inverse=True)
+    rows = torch.full((uniq.numel(),), -1, dtype=torch.int32, device=ids_col.device)
+    col = ids_col.contiguous()
+    for c0 in range(0, uniq.numel(), FIND_CHUNK):
+        ext().index_find_ids(col, uniq[c0:c0 + FIND_CHUNK], rows[c0:c0 + FIND_CHUNK])
+    return rows[inv]
 
 
 # -- ingest dedup: near-duplicate detection (csrc/ingest_dedup.hip) ----------

@@ -66,26 +66,40 @@ def globalize_ids(ids: torch.Tensor, rank: int, shard_rows: int) -> torch.Tensor
 
 
 def merge_topk_candidates(
-    scores: torch.Tensor, ids: torch.Tensor, rank: int, batch: int, world: int, k: int
-) -> Tuple[torch.Tensor, torch.Tensor]:
+    scores: torch.Tensor, ids: torch.Tensor, rank: int, batch: int, world: int, k: int,
+    payload: Optional[torch.Tensor] = None,
+):
     """Each rank scored ALL (world*batch) queries against ITS shard.
     All-gather candidates, keep my query rows, merge to final top-k.
 
     scores/ids: [world*batch, k] local candidates (ids already global).
     Returns [batch, k] for THIS rank's queries.
+
+    payload: one more [world*batch, k] tensor that belongs to the
+    candidates slot by slot (the rows' memory ids); it is gathered and
+    selected like the ids and returned as a third tensor. Without a
+    payload the result is the (scores, ids) pair.
     """
     if world <= 1:
-        return scores[:batch], ids[:batch]
+        if payload is None:
+            return scores[:batch], ids[:batch]
+        return scores[:batch], ids[:batch], payload[:batch]
     nq = scores.shape[0]
-    cand_s = torch.empty(world, nq, k, dtype=scores.dtype, device=scores.device)
-    cand_i = torch.empty(world, nq, k, dtype=ids.dtype, device=ids.device)
-    dist.all_gather_into_tensor(cand_s, scores.unsqueeze(0).contiguous())
-    dist.all_gather_into_tensor(cand_i, ids.unsqueeze(0).contiguous())
     my0 = rank * batch
-    mine_s = cand_s[:, my0 : my0 + batch].permute(1, 0, 2).reshape(batch, world * k)
-    mine_i = cand_i[:, my0 : my0 + batch].permute(1, 0, 2).reshape(batch, world * k)
+
+    def gather_mine(t):
+        cand = torch.empty(world, nq, k, dtype=t.dtype, device=t.device)
+        dist.all_gather_into_tensor(cand, t.unsqueeze(0).contiguous())
+        return cand[:, my0 : my0 + batch].permute(1, 0, 2).reshape(batch, world * k)
+
+    mine_s = gather_mine(scores)
+    mine_i = gather_mine(ids)
     top = torch.topk(mine_s, k, dim=1)
-    return top.values, torch.gather(mine_i, 1, top.indices)
+    if payload is None:
+        return top.values, torch.gather(mine_i, 1, top.indices)
+    mine_p = gather_mine(payload)
+    return (top.values, torch.gather(mine_i, 1, top.indices),
+            torch.gather(mine_p, 1, top.indices))
 
 
 def local_shard_ids(flat_ids: torch.Tensor, rank: int, shard_rows: int) -> torch.Tensor:

@@ -32,7 +32,10 @@ messages:
      salience rows and is compacted in place (csrc/index_forget.hip);
      with ingest_dedup a message within the threshold of a recalled row
      reinforces that row instead, and near-duplicates within the step are
-     stored once (csrc/ingest_dedup.hip)
+     stored once (csrc/ingest_dedup.hip); with memory_ids every row
+     carries a stable int64 id that moves with it (csrc/index_ids.hip
+     finds the row of an id), and save_memory / load_memory carry the
+     live rows over a restart
 
 Multi-GPU (one process per GPU, torch.distributed over RCCL/xGMI):
 the index is sharded across ranks; recall queries are all-gathered so
@@ -45,11 +48,15 @@ rows.
 
 from __future__ import annotations
 
+import hashlib
+import json
 import math
+import os
+import shutil
 import threading
 import time
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -60,6 +67,50 @@ from ..parallel import collectives as coll
 from .synth import SynthBatch
 
 V_DENY = 3  # csrc/firewall.hip verdict code
+
+# memory id layout (PipelineConfig.memory_ids): a non-negative int64, -1 =
+# none. bit 62 = preloaded row, bits 48..61 = rank, bits 0..47 = sequence
+MEM_ID_PRELOADED = 1 << 62
+MEM_ID_RANK_SHIFT = 48
+MEM_ID_RANKS = 1 << 14
+MEM_ID_SEQS = 1 << 48
+
+
+def make_memory_id(rank: int, seq: int, preloaded: bool = False) -> int:
+    """The memory id of sequence number `seq` on `rank`: an ingested
+    message's seq is its position in the rank's message stream
+    (FirewallPipeline.messages_seen), a preloaded row's seq its row."""
+    rank, seq = int(rank), int(seq)
+    if not 0 <= rank < MEM_ID_RANKS:
+        raise ValueError(f"memory id: rank {rank} outside [0, {MEM_ID_RANKS})")
+    if not 0 <= seq < MEM_ID_SEQS:
+        raise ValueError(f"memory id: sequence {seq} outside [0, 2^48)")
+    return (MEM_ID_PRELOADED if preloaded else 0) | (rank << MEM_ID_RANK_SHIFT) | seq
+
+
+def split_memory_id(mem_id: int) -> Tuple[bool, int, int]:
+    """(preloaded, rank, seq) of a memory id."""
+    mem_id = int(mem_id)
+    if not 0 <= mem_id < (1 << 63):
+        raise ValueError(f"not a memory id: {mem_id}")
+    return (bool(mem_id & MEM_ID_PRELOADED),
+            (mem_id >> MEM_ID_RANK_SHIFT) & (MEM_ID_RANKS - 1),
+            mem_id & (MEM_ID_SEQS - 1))
+
+
+def _row_bytes(t: torch.Tensor) -> int:
+    return math.prod(t.shape[1:]) * t.element_size()
+
+
+MEMORY_FORMAT = 1
+# pinned staging of save_memory / load_memory, whatever the row count
+MEMORY_STAGING_BYTES = 16 << 20
+_MEMORY_FILES = {  # column -> file in the snapshot directory
+    "index": "index.bf16",
+    "salience": "salience.f32",
+    "owner": "owner.i32",
+    "ids": "ids.i64",
+}
 
 
 @dataclass
@@ -131,6 +182,11 @@ class PipelineConfig:
     # stored, and of several such messages in one step only the first is
     # stored (FirewallPipeline._dedup states the rule). Needs ingest.
     ingest_dedup: float = 0.0
+    # stable memory ids: an int64 per index row (8 B) that moves with the
+    # row at a forget (make_memory_id states the layout); step() then
+    # also returns recall_mem_ids and memory_ids, and rows can be found
+    # and forgotten by id (FirewallPipeline.memory_rows, forget(ids=))
+    memory_ids: bool = False
 
     def __post_init__(self):
         if self.ingest_dedup != 0.0:
@@ -184,6 +240,10 @@ class FirewallPipeline:
         self.world_size = world_size
         self.rank = rank
         self.batch_seq = 0
+        # messages given to step() so far: the sequence number of the next
+        # message's memory id (batch_seq * B is not unique when the batch
+        # size varies)
+        self.messages_seen = 0
         self.profiler = StageProfiler(profile)
         torch.manual_seed(cfg.seed + rank)
 
@@ -288,6 +348,15 @@ class FirewallPipeline:
                 self.owner_counts = torch.bincount(
                     self.index_owner[:cfg.index_size].long(), minlength=cfg.n_agents)
 
+            # memory ids: preloaded rows carry the preload bit and their row
+            self.index_ids = None
+            if cfg.memory_ids:
+                self.index_ids = torch.full((cap,), -1, dtype=torch.int64, device=self.device)
+                # raises if the rank or the last row does not fit the layout
+                make_memory_id(rank, max(cfg.index_size - 1, 0), preloaded=True)
+                self.index_ids[:cfg.index_size] = make_memory_id(rank, 0, preloaded=True) + \
+                    torch.arange(cfg.index_size, dtype=torch.int64, device=self.device)
+
             # hot-band caches for threshold_banded recall; refreshed every
             # band_refresh_steps as reinforcement reshapes the salience
             self.hot_idx = None
@@ -352,16 +421,29 @@ class FirewallPipeline:
         self.is_hot = torch.zeros(self.capacity, dtype=torch.bool, device=self.device)
         self.is_hot[self.hot_idx] = True
 
+    def memory_rows(self, ids: Union[torch.Tensor, Sequence[int]]) -> torch.Tensor:
+        """The rows of this rank's shard that hold the given memory ids
+        now: int32 on the device, one per id, -1 for an id that was
+        forgotten or never handed out here (g.find_rows). A row number is
+        good until the next forget; the id stays."""
+        if self.index_ids is None:
+            raise ValueError("memory_rows needs PipelineConfig.memory_ids")
+        want = torch.as_tensor(ids, dtype=torch.int64).reshape(-1).to(self.device)
+        return g.find_rows(self.index_ids[:self.n_rows], want)
+
     def forget(self, count: Optional[int] = None,
-               min_salience: Optional[float] = None) -> int:
+               min_salience: Optional[float] = None,
+               ids: Union[torch.Tensor, Sequence[int], None] = None) -> int:
         """Forget live rows of this rank's shard and compact the index in
         place. Exactly one argument is given: `count` forgets the `count`
         lowest-salience live rows (g.evict_mask: ties go by row index);
         `min_salience` forgets every live row with salience <=
-        min_salience (the store's prune rule; operators would pass 0.02).
-        Returns the number of rows forgotten.
+        min_salience (the store's prune rule; operators would pass 0.02);
+        `ids` (a 1-D int64 tensor or a sequence, memory_ids only) forgets
+        the rows that hold those memory ids, ignoring ids no row holds and
+        repeats. Returns the number of rows forgotten.
 
-        Index, fp4 copy, owners and salience are compacted by one
+        Index, fp4 copy, owners, salience and memory ids are compacted by one
         g.index_forget (hole filling, csrc/index_forget.hip): survivors
         from the tail move into the holes, so row order is not preserved
         and row ids change. recall_ids returned by earlier steps name rows
@@ -369,16 +451,20 @@ class FirewallPipeline:
         contents of rows [n_rows, capacity) are unspecified afterwards;
         nothing reads them. Rank-local: no collective, global ids keep the
         capacity stride."""
-        if (count is None) == (min_salience is None):
-            raise ValueError("forget: give exactly one of count and min_salience")
+        if (count is not None) + (min_salience is not None) + (ids is not None) != 1:
+            raise ValueError("forget: give exactly one of count, min_salience and ids")
         if self.index8 is not None:
             raise ValueError("forget: no move path for the e4m3 index copy")
         n = self.n_rows
         sal = self.salience[:n]
         if count is not None:
             dead = g.evict_mask(sal, count)
-        else:
+        elif min_salience is not None:
             dead = sal <= float(min_salience)
+        else:
+            rows = self.memory_rows(ids).long()
+            dead = torch.zeros(n, dtype=torch.bool, device=self.device)
+            dead[rows[rows >= 0]] = True
         gone = None
         if self.owner_counts is not None:
             # taken before the move: afterwards the rows hold other owners
@@ -388,7 +474,8 @@ class FirewallPipeline:
                                   minlength=A + 1)[:A]
         x4, xs = self.index4 if self.index4 is not None else (None, None)
         n_new = g.index_forget(dead, index=self.index, X4=x4, XS=xs,
-                               owner=self.index_owner, salience=self.salience)
+                               owner=self.index_owner, salience=self.salience,
+                               ids=self.index_ids)
         removed = n - n_new
         if removed == 0:
             return 0
@@ -415,9 +502,10 @@ class FirewallPipeline:
         return 0 if self._merged is None else int(self._merged[1])
 
     def _dedup(self, feats: torch.Tensor, keep: torch.Tensor, agent_idx: torch.Tensor,
-               recall_ids: torch.Tensor) -> torch.Tensor:
+               recall_ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """The ingest_dedup rule for one step; returns the bool mask of the
-        messages to store. tau = cfg.ingest_dedup; similarity is the plain
+        messages to store, and dup_row (int32 [B]: the row a message
+        reinforced, else -1). tau = cfg.ingest_dedup; similarity is the plain
         dot of the bf16 feature rows, as recall scores it; with
         recall_isolation only rows of the same agent can be duplicates.
 
@@ -467,10 +555,11 @@ class FirewallPipeline:
         first = g.batch_first_similar(feats, elig, tau, owner=qowner)
         store = first == torch.arange(first.numel(), dtype=torch.int32, device=first.device)
         self._merged += torch.stack([in_index.sum(), (elig & ~store).sum()])
-        return store
+        return store, dup_row
 
     def _ingest(self, feats: torch.Tensor, verdict: torch.Tensor,
-                agent_idx: torch.Tensor, recall_ids: Optional[torch.Tensor] = None) -> None:
+                agent_idx: torch.Tensor,
+                recall_ids: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
         """Remember this step's messages: append every feature row whose
         verdict is not deny to the live index (bf16 row, fp4 codes and
         scales, owner, salience 1.0) with one g.index_append launch. The
@@ -482,10 +571,21 @@ class FirewallPipeline:
         results do not change, and only a step that keeps more messages
         than the whole capacity still drops the excess. With ingest_dedup
         the rows to store are those _dedup leaves, found before any
-        eviction, and "kept" below counts them."""
+        eviction, and "kept" below counts them.
+
+        With memory_ids returns the step's `memory_ids` (int64 [B]): a
+        stored message's own id (rank and messages_seen + its batch
+        position), the id of the row a merged message reinforced (read
+        before any eviction), -1 for the rest."""
         keep = verdict != V_DENY
+        mem = None
+        if self.index_ids is not None:
+            mem = torch.full((keep.numel(),), -1, dtype=torch.int64, device=self.device)
         if self.cfg.ingest_dedup > 0.0:
-            keep = self._dedup(feats, keep, agent_idx, recall_ids)
+            keep, dup_row = self._dedup(feats, keep, agent_idx, recall_ids)
+            if mem is not None:
+                mem = torch.where(dup_row >= 0,
+                                  self.index_ids[dup_row.clamp_min(0).long()], mem)
         src = torch.nonzero(keep).flatten().to(torch.int32)
         kept = int(src.numel())
         free = self.capacity - self.n_rows
@@ -495,20 +595,263 @@ class FirewallPipeline:
         take = min(kept, self.capacity - self.n_rows)
         self.ingest_dropped += kept - take
         if take == 0:
-            return
+            return mem
         src = src[:take]
         x4, xs = self.index4 if self.index4 is not None else (None, None)
         owner_src = None
         if self.index_owner is not None:
             owner_src = agent_idx.to(torch.int32)
+        id_base = 0
+        if mem is not None:
+            make_memory_id(self.rank, self.messages_seen + keep.numel() - 1)  # raises at 2^48
+            id_base = make_memory_id(self.rank, self.messages_seen)
+            mem[src.long()] = id_base + src.long()
         g.index_append(
             feats, src, self.n_rows, self.index, x4, xs,
             owner_dst=self.index_owner, owner_src=owner_src,
-            salience_dst=self.salience, salience_init=1.0)
+            salience_dst=self.salience, salience_init=1.0,
+            id_dst=self.index_ids, id_base=id_base)
         if self.owner_counts is not None:
             owners = owner_src[src.long()].long()
             self.owner_counts.index_add_(0, owners, torch.ones_like(owners))
         self.n_rows += take
+        return mem
+
+    def _row_mem_ids(self, rows: torch.Tensor) -> torch.Tensor:
+        """int64, shaped like `rows`: the memory ids of shard-local rows,
+        -1 where a slot is empty (row -1)."""
+        got = self.index_ids[rows.long().clamp_min(0)]
+        return torch.where(rows >= 0, got, torch.full_like(got, -1))
+
+    # -- snapshot and restore ----------------------------------------------
+    _COUNTERS = ("messages_seen", "batch_seq", "_steps_done", "forgotten", "forget_epoch",
+                 "ingest_dropped", "recall_overflowed", "recall_rescanned",
+                 "recall_direct_fallbacks")
+
+    def _memory_columns(self) -> Dict[str, torch.Tensor]:
+        cols = {"index": self.index, "salience": self.salience}
+        if self.index_owner is not None:
+            cols["owner"] = self.index_owner
+        if self.index_ids is not None:
+            cols["ids"] = self.index_ids
+        return cols
+
+    def _embed_sha256(self, staging: torch.Tensor) -> str:
+        """sha256 over the bytes of the encoder table, read through the
+        pinned staging buffer."""
+        h = hashlib.sha256()
+        flat = self.embed.reshape(-1).view(torch.uint8)
+        for b0 in range(0, flat.numel(), staging.numel()):
+            nb = min(staging.numel(), flat.numel() - b0)
+            staging[:nb].copy_(flat[b0:b0 + nb])
+            h.update(staging[:nb].numpy().data)
+        return h.hexdigest()
+
+    def save_memory(self, path: str, chunk_rows: Optional[int] = None) -> Dict[str, Any]:
+        """Write this rank's live memory to the new directory `path`;
+        returns the manifest. Several ranks each save to a directory of
+        their own.
+
+        manifest.json holds the format version, dim, n_rows, rank and
+        world size, which columns are present, every file's byte size, the
+        counters and a sha256 of the encoder table; index.bf16,
+        salience.f32, owner.i32 and ids.i64 hold the live prefix [:n_rows]
+        of their column as a raw little-endian array; state.npz holds the
+        trust and cortex state. The MXFP4 copy is not stored: load_memory
+        requantizes the rows, which gives the same bits.
+
+        Device-to-host copies go through one pinned staging buffer of
+        MEMORY_STAGING_BYTES (16 MiB), whatever n_rows is; chunk_rows
+        lowers the rows per copy below what the buffer holds. Everything
+        is written into a temporary sibling directory, files and directory
+        are fsynced, and the directory is renamed into place. An existing
+        `path` is never overwritten: ValueError."""
+        path = os.path.abspath(path)
+        if os.path.lexists(path):
+            raise ValueError(f"save_memory: {path} exists; snapshots are never overwritten")
+        if chunk_rows is not None and chunk_rows < 1:
+            raise ValueError("save_memory: chunk_rows must be positive")
+        n = self.n_rows
+        staging = torch.empty(MEMORY_STAGING_BYTES, dtype=torch.uint8, pin_memory=True)
+        tmp = f"{path}.tmp-{os.getpid()}"
+        os.mkdir(tmp)
+
+        def write_file(name, fill):
+            with open(os.path.join(tmp, name), "wb") as f:
+                fill(f)
+                f.flush()
+                os.fsync(f.fileno())
+            return os.path.getsize(os.path.join(tmp, name))
+
+        def sync_dir(d):
+            fd = os.open(d, os.O_RDONLY)
+            try:
+                os.fsync(fd)
+            finally:
+                os.close(fd)
+
+        try:
+            files = {}
+            for col, t in self._memory_columns().items():
+                row_bytes = _row_bytes(t)
+                rows = max(1, MEMORY_STAGING_BYTES // row_bytes)
+                if chunk_rows is not None:
+                    rows = min(rows, chunk_rows)
+
+                def fill(f, t=t, rows=rows, row_bytes=row_bytes):
+                    for r0 in range(0, n, rows):
+                        r1 = min(n, r0 + rows)
+                        nb = (r1 - r0) * row_bytes
+                        staging[:nb].copy_(t[r0:r1].reshape(-1).view(torch.uint8))
+                        f.write(staging[:nb].numpy().data)
+
+                files[_MEMORY_FILES[col]] = write_file(_MEMORY_FILES[col], fill)
+
+            state = {f"trust/{k}": v.cpu().numpy() for k, v in self.trust_state.items()}
+            state.update({f"cortex/{k}": v.cpu().numpy() for k, v in self.cortex_state.items()})
+            files["state.npz"] = write_file("state.npz", lambda f: np.savez(f, **state))
+
+            counters = {k: int(getattr(self, k)) for k in self._COUNTERS}
+            counters["ingest_merged_index"] = self.ingest_merged_index
+            counters["ingest_merged_batch"] = self.ingest_merged_batch
+            manifest = {
+                "format": MEMORY_FORMAT,
+                "dim": self.cfg.dim,
+                "n_rows": n,
+                "rank": self.rank,
+                "world_size": self.world_size,
+                "columns": {"owner": self.index_owner is not None,
+                            "ids": self.index_ids is not None},
+                "files": files,
+                "counters": counters,
+                "embed_sha256": self._embed_sha256(staging),
+            }
+            write_file("manifest.json",
+                       lambda f: f.write(json.dumps(manifest, indent=1, sort_keys=True).encode()))
+            sync_dir(tmp)
+        except BaseException:
+            shutil.rmtree(tmp, ignore_errors=True)
+            raise
+        if os.path.lexists(path):
+            raise ValueError(f"save_memory: {path} appeared while saving; left {tmp}")
+        os.rename(tmp, path)
+        sync_dir(os.path.dirname(path))
+        return manifest
+
+    def load_memory(self, path: str) -> Dict[str, Any]:
+        """Replace this rank's live memory by the snapshot in `path`
+        (save_memory); returns the manifest.
+
+        Everything is checked before any state is touched, and a snapshot
+        that does not fit raises ValueError: an unknown format version, a
+        file whose size is not what the manifest and n_rows give, another
+        dim, more rows than this pipeline's capacity, owner or id columns
+        on one side only, another rank or world size, another encoder
+        table (sha256), or a pipeline with the e4m3 index copy.
+
+        Then the live rows [:n_rows] of every column are replaced,
+        whatever the pipeline was built with; the MXFP4 copy is requantized
+        in place (one launch; the same bits the append kernel wrote);
+        owner_counts is recounted; the counters and the trust and cortex
+        state are restored; messages_seen continues, so ids handed out
+        afterwards are new. forget_epoch becomes max(current, saved) + 1:
+        row numbers held from before the load are stale. threshold_banded
+        recall rebuilds its hot band from the loaded salience, so until
+        the next scheduled refresh a restored pipeline may recall
+        differently from one that was never interrupted. Not restored:
+        the encoder and classifier weights, the fact table and whatever
+        the audit sink has written.
+
+        Host-to-device copies go through the same 16 MiB pinned staging as
+        save_memory."""
+        path = os.path.abspath(path)
+        try:
+            with open(os.path.join(path, "manifest.json"), "rb") as f:
+                man = json.loads(f.read().decode())
+        except (OSError, ValueError) as exc:
+            raise ValueError(f"load_memory: no readable manifest in {path}: {exc}") from exc
+
+        def bad(why):
+            raise ValueError(f"load_memory: {path}: {why}")
+
+        if man.get("format") != MEMORY_FORMAT:
+            bad(f"format version {man.get('format')!r}, this code reads {MEMORY_FORMAT}")
+        if self.index8 is not None:
+            bad("this pipeline keeps the e4m3 index copy, which has no load path")
+        for k in ("dim", "n_rows", "rank", "world_size", "columns", "files", "counters",
+                  "embed_sha256"):
+            if k not in man:
+                bad(f"the manifest lacks {k!r}")
+        for k in self._COUNTERS + ("ingest_merged_index", "ingest_merged_batch"):
+            if not isinstance(man["counters"].get(k), int):
+                bad(f"the manifest lacks the counter {k!r}")
+        if man["dim"] != self.cfg.dim:
+            bad(f"dim {man['dim']}, this pipeline has {self.cfg.dim}")
+        n = int(man["n_rows"])
+        if not 0 <= n <= self.capacity:
+            bad(f"{n} rows, this pipeline's capacity is {self.capacity}")
+        cols = self._memory_columns()
+        for col in ("owner", "ids"):
+            if bool(man["columns"].get(col)) != (col in cols):
+                bad(f"the {col} column is present on one side only")
+        if man["rank"] != self.rank or man["world_size"] != self.world_size:
+            bad(f"saved by rank {man['rank']} of {man['world_size']}, "
+                f"this is rank {self.rank} of {self.world_size}")
+        for col, t in cols.items():
+            name = _MEMORY_FILES[col]
+            want = n * _row_bytes(t)
+            try:
+                size = os.path.getsize(os.path.join(path, name))
+            except OSError:
+                bad(f"{name} is missing")
+            if size != want or man["files"].get(name) != want:
+                bad(f"{name} holds {size} bytes, {n} rows need {want}")
+        try:
+            if os.path.getsize(os.path.join(path, "state.npz")) != man["files"].get("state.npz"):
+                bad("state.npz differs in size from the manifest")
+            with np.load(os.path.join(path, "state.npz")) as z:
+                state = {k: z[k] for k in z.files}
+        except (OSError, ValueError, KeyError) as exc:
+            bad(f"state.npz is unreadable: {exc}")
+        groups = (("trust", self.trust_state), ("cortex", self.cortex_state))
+        for prefix, d in groups:
+            for k, v in d.items():
+                a = state.get(f"{prefix}/{k}")
+                if a is None or tuple(a.shape) != tuple(v.shape):
+                    bad(f"state.npz lacks {prefix}/{k} of shape {tuple(v.shape)}")
+        staging = torch.empty(MEMORY_STAGING_BYTES, dtype=torch.uint8, pin_memory=True)
+        if man["embed_sha256"] != self._embed_sha256(staging):
+            bad("saved under another encoder table; its rows mean nothing here")
+
+        for col, t in cols.items():
+            row_bytes = _row_bytes(t)
+            rows = max(1, MEMORY_STAGING_BYTES // row_bytes)
+            with open(os.path.join(path, _MEMORY_FILES[col]), "rb") as f:
+                for r0 in range(0, n, rows):
+                    r1 = min(n, r0 + rows)
+                    nb = (r1 - r0) * row_bytes
+                    if f.readinto(staging[:nb].numpy().data) != nb:
+                        raise OSError(f"load_memory: short read of {_MEMORY_FILES[col]}")
+                    t[r0:r1].reshape(-1).view(torch.uint8).copy_(staging[:nb])
+        if self.index4 is not None and n:
+            g.quantize_fp4_mx(self.index[:n], out=(self.index4[0][:n], self.index4[1][:n]))
+        self.n_rows = n
+        if self.owner_counts is not None:
+            self.owner_counts = torch.bincount(self.index_owner[:n].long(),
+                                               minlength=self.owner_counts.numel())
+        for prefix, d in groups:
+            for k, v in d.items():
+                v.copy_(torch.from_numpy(state[f"{prefix}/{k}"]))
+        epoch = self.forget_epoch
+        for k in self._COUNTERS:
+            setattr(self, k, int(man["counters"][k]))
+        self.forget_epoch = max(epoch, self.forget_epoch) + 1
+        if self._merged is not None:
+            self._merged.copy_(torch.tensor([man["counters"]["ingest_merged_index"],
+                                             man["counters"]["ingest_merged_batch"]]))
+        if self.cfg.recall_mode == "threshold_banded":
+            self._refresh_hot_band()
+        return man
 
     # -- input staging -----------------------------------------------------
     def stage(self, batch: SynthBatch) -> Dict[str, torch.Tensor]:
@@ -646,14 +989,23 @@ class FirewallPipeline:
             if self.index_owner is not None:
                 qo_all = coll.allgather_owners(agent_idx.to(torch.int32), self.world_size)
             scores, ids = local_recall(q_all, qo_all)
+            # memory ids are read from this shard, before the ids turn global
+            mem_local = None if self.index_ids is None else self._row_mem_ids(ids)
             # shard id stride = the shard's capacity (== index_size without ingest)
             ids = coll.globalize_ids(ids.to(torch.int32), self.rank, self.capacity)
-            recall_scores, recall_ids = coll.merge_topk_candidates(
-                scores, ids, self.rank, B, self.world_size, cfg.topk
-            )
+            if mem_local is None:
+                recall_scores, recall_ids = coll.merge_topk_candidates(
+                    scores, ids, self.rank, B, self.world_size, cfg.topk
+                )
+            else:
+                recall_scores, recall_ids, recall_mem_ids = coll.merge_topk_candidates(
+                    scores, ids, self.rank, B, self.world_size, cfg.topk, payload=mem_local
+                )
         else:
             recall_scores, recall_ids = local_recall(
                 feats, agent_idx.to(torch.int32) if self.index_owner is not None else None)
+            if self.index_ids is not None:
+                recall_mem_ids = self._row_mem_ids(recall_ids)
 
         # salience reinforcement + decay (Membrane recall semantics)
         if self.world_size > 1:
@@ -716,17 +1068,21 @@ class FirewallPipeline:
             ),
         )
 
+        memory_ids = None
         if cfg.ingest:
             prof.mark("ingest")
-            self._ingest(feats, verdict, agent_idx, recall_ids)
+            memory_ids = self._ingest(feats, verdict, agent_idx, recall_ids)
+        elif self.index_ids is not None:
+            memory_ids = torch.full((B,), -1, dtype=torch.int64, device=self.device)
 
         prof.mark("end")
         self.batch_seq += 1
+        self.messages_seen += B
         self._steps_done += 1
         if self.audit_sink is not None:
             self.audit_sink(records, root)
 
-        return {
+        res = {
             "verdict": verdict,
             "risk": risk,
             "logits": logits,
@@ -741,6 +1097,11 @@ class FirewallPipeline:
             "validation": validation,
             "cortex": self.cortex_state,
         }
+        if self.index_ids is not None:
+            # the recalled rows' ids as of the recall, and each message's own
+            res["recall_mem_ids"] = recall_mem_ids
+            res["memory_ids"] = memory_ids
+        return res
 
 
 class AsyncAuditWriter:

@@ -129,6 +129,11 @@ class FirewallService:
         hits = {k: v.to("cpu").numpy() for k, v in res.get("hits", {}).items()}
         recall_ids = res.get("recall_ids")
         recall_ids = recall_ids.to("cpu").numpy() if recall_ids is not None else None
+        # stable memory ids (PipelineConfig.memory_ids); absent otherwise
+        mem_ids = res.get("memory_ids")
+        mem_ids = mem_ids.to("cpu").numpy() if mem_ids is not None else None
+        recall_mem = res.get("recall_mem_ids")
+        recall_mem = recall_mem.to("cpu").numpy() if recall_mem is not None else None
         self.stats["batches"] += 1
         self.stats["messages"] += len(batch)
         self.stats["maxBatch"] = max(self.stats["maxBatch"], len(batch))
@@ -140,6 +145,10 @@ class FirewallService:
                 "hits": {k: int(v[i]) for k, v in hits.items()},
                 "recallIds": recall_ids[i].tolist() if recall_ids is not None else [],
             })
+            if mem_ids is not None:
+                out[-1]["memoryId"] = int(mem_ids[i])
+            if recall_mem is not None:
+                out[-1]["recallMemoryIds"] = recall_mem[i].tolist()
         return out
 
     def close(self) -> None:
