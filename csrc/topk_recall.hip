@@ -921,24 +921,43 @@ DEVINL void stage_scale_rows(const uint8_t* __restrict__ src, int sb,
                              long long row0, long long row_max,
                              uint8_t* lds_base, int tile_rows) {
   // scale sheet: tile_rows x sb bytes, staged as LINEAR bytes (no
-  // swizzle: the consumers are byte reads). row0*sb is 16-aligned
-  // (row0 is a multiple of 256); the trailing piece clamps to the last
-  // aligned 16 B inside the buffer — garbage scales only ever land on
-  // rows the epilogue bound-checks away.
+  // swizzle: the consumers are byte reads). A piece that starts past the
+  // array's last whole piece is taken from that last piece, so every byte
+  // of a live row comes from its own place and garbage scales only ever
+  // land on rows the epilogue bound-checks away. That needs a piece that
+  // never straddles the array's end: 16 B pieces when rows are whole
+  // 16 B multiples (sb % 16 == 0; row0*sb is 16-aligned, row0 being a
+  // multiple of 256), dword pieces otherwise (sb is always a multiple of
+  // 4). The sheet is a multiple of 64 pieces either way, so whole waves
+  // issue. The dword path is off the production depths (D = 512, 1024).
   long long base = row0 * (long long)sb;
-  long long last = ((row_max * (long long)sb) >> 4) * 16 - 16;
-  if (last < 0) last = 0;
-  int n_pieces = (tile_rows * sb + 15) / 16;
+  long long total = row_max * (long long)sb;
   int w = wave_id();
   int lane = lane_id();
-  for (int piece0 = w * WAVE; piece0 < n_pieces; piece0 += TK_THREADS) {
-    int piece = piece0 + lane;
-    long long off = base + (long long)piece * 16;
-    if (off > last) off = last;
-    int piece0_u = __builtin_amdgcn_readfirstlane(piece0);
-    auto ldst = (AS3 char*)lds_base + piece0_u * 16;
-    __builtin_amdgcn_global_load_lds((const AS1 void*)(src + off),
-                                     (AS3 void*)ldst, 16, 0, 0);
+  if ((sb & 15) == 0) {
+    long long last = total - 16;
+    int n_pieces = tile_rows * sb / 16;
+    for (int piece0 = w * WAVE; piece0 < n_pieces; piece0 += TK_THREADS) {
+      int piece = piece0 + lane;
+      long long off = base + (long long)piece * 16;
+      if (off > last) off = last;
+      int piece0_u = __builtin_amdgcn_readfirstlane(piece0);
+      auto ldst = (AS3 char*)lds_base + piece0_u * 16;
+      __builtin_amdgcn_global_load_lds((const AS1 void*)(src + off),
+                                       (AS3 void*)ldst, 16, 0, 0);
+    }
+  } else {
+    long long last = total - 4;
+    int n_pieces = tile_rows * sb / 4;
+    for (int piece0 = w * WAVE; piece0 < n_pieces; piece0 += TK_THREADS) {
+      int piece = piece0 + lane;
+      long long off = base + (long long)piece * 4;
+      if (off > last) off = last;
+      int piece0_u = __builtin_amdgcn_readfirstlane(piece0);
+      auto ldst = (AS3 char*)lds_base + piece0_u * 4;
+      __builtin_amdgcn_global_load_lds((const AS1 void*)(src + off),
+                                       (AS3 void*)ldst, 4, 0, 0);
+    }
   }
 }
 
@@ -2007,8 +2026,8 @@ topk_scan_fp4_v7_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
 //    registers. Thread t owns half row (row = t & 255, grp = t >> 8, so
 //    grp is wave-uniform): one global_load_dwordx4 of the half row when
 //    rows are whole 16 B pieces (np = 4, 8), else one dword load per
-//    dword that exists (min(4, np - 4*grp), block-uniform branch), each
-//    taken from where v7's staging takes it (scale9_src), 8 v_perm_b32
+//    dword that exists (min(4, np - 4*grp), block-uniform branch), rows
+//    past the array's end clamped as v7's staging clamps them, 8 v_perm_b32
 //    for the 4x4 byte transpose, two ds_write_b64. Q sheet: once per block, ahead of the
 //    prologue barrier. X sheet: single buffer, written at the tile head
 //    from registers loaded one tile earlier (the first tile's in the
@@ -2040,36 +2059,23 @@ topk_scan_fp4_v7_kernel(const uint8_t* __restrict__ Q4, const uint8_t* __restric
 typedef uint32_t u32x2_s9 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4_s9 __attribute__((ext_vector_type(4)));
 
-// Where stage_scale_rows (v1..v7) takes sheet byte o of a [rows][sb] scale
-// array from: it stages 16 B pieces and clamps a piece that starts past
-// `last` (the last whole 16 B of the array) onto it. For sb % 16 == 0 that
-// only ever moves rows past the array's end. For other row pitches pieces
-// straddle rows and the clamp also moves the tail of a live last row whose
-// piece sticks out of the array (rows * sb not a multiple of 16). v9 takes
-// every dword from the same place, so the kernels stay interchangeable bit
-// for bit at every shape; changing that rule belongs to all of them at once
-// (docs/NOTES-NEXT.md).
-DEVINL long long scale9_src(long long o, long long last) {
-  long long piece = o & ~15LL;
-  return (piece > last ? last : piece) + (o & 15LL);
-}
-
 // the nd (0..4, wave-uniform) dwords of the half scale row at array byte
 // offset o; w[pl] holds the four kgrp bytes of pair 4*grp + pl, absent
 // pairs read as 0. whole16: sb % 16 == 0, the half row is one 16 B piece.
+// A load that would start past the array's end (a row past the last live
+// one) is moved onto the array's last piece, as stage_scale_rows does; a
+// live row's bytes always come from their own place.
 DEVINL u32x4_s9 scale9_load(const uint8_t* __restrict__ src, long long o,
                             long long total, int nd, bool whole16) {
-  long long last = (total >> 4) * 16 - 16;
-  if (last < 0) last = 0;
   u32x4_s9 w = {0u, 0u, 0u, 0u};
   if (whole16) {
-    __builtin_memcpy(&w, src + scale9_src(o, last), 16);
+    __builtin_memcpy(&w, src + min(o, total - 16), 16);
   } else {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if (i < nd) {
         uint32_t t;
-        __builtin_memcpy(&t, src + min(scale9_src(o + 4 * i, last), total - 4), 4);
+        __builtin_memcpy(&t, src + min(o + 4 * i, total - 4), 4);
         w[i] = t;
       }
   }

@@ -113,8 +113,7 @@ def test_hist_scan_and_rescan(family, shape, owned):
     rows = over.nonzero(as_tuple=True)[0]
     assert torch.isfinite(theta2[rows]).all()
     th2 = theta2[rows]
-    # the plain v10 / owned kernels on the gathered rows (padded to a
-    # multiple of 4 rows: see ops.gpu.fp4x4_rescan)
+    # the plain v10 / owned kernels on the gathered rows
     cs2, ci2, cn2 = g.fp4x4_rescan(
         c["Q4"], c["QS"], (c["X4"], c["XS"]), theta2, rows, CAP,
         own.get("xowner"), own.get("qowner"), n_swaths=c["S"])

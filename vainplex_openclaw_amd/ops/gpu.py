@@ -356,6 +356,59 @@ def fp4_mx_spec(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return out4, outs
 
 
+_E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def reference_fp4_decode(P4: torch.Tensor, S: torch.Tensor,
+                         natural_order: bool = False) -> torch.Tensor:
+    """MXFP4 rows back to numbers, in fp64 [n, D]: P4 = packed e2m1
+    nibbles [n, D/2] (low nibble = even position), S = e8m0 scales
+    [n, D/32]. Nibble = sign bit, then an index into the e2m1 grid; byte
+    j's two elements are times 2^(S[:, j // 16] - 127). Every value is
+    exact in fp64. The result is in the stored (fragment) order of
+    to_fp4_mx; natural_order=True undoes fp4_perm128 per 128-chunk.
+    Plain torch, device agnostic, independent of the extension."""
+    n, half = P4.shape
+    D = half * 2
+    assert P4.dtype == torch.uint8 and S.dtype == torch.uint8
+    assert S.shape == (n, D // 32)
+    grid = torch.tensor(_E2M1_GRID, dtype=torch.float64, device=P4.device)
+    codes = torch.stack([P4 & 0xF, P4 >> 4], dim=2).reshape(n, D).long()
+    mag = grid[codes & 7]
+    val = torch.where(codes >= 8, -mag, mag)
+    scale = torch.exp2(S.to(torch.float64) - 127.0).repeat_interleave(32, dim=1)
+    dec = val * scale
+    if not natural_order:
+        return dec
+    p128 = fp4_perm128().to(P4.device)
+    perm = (torch.arange(0, D, 128, device=P4.device).unsqueeze(1) + p128.unsqueeze(0)).reshape(-1)
+    out = torch.empty_like(dec)
+    out[:, perm] = dec
+    return out
+
+
+def reference_scores_bound(q: torch.Tensor, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp64 q @ x.T of two decoded operands [nq, D], [nx, D] and the
+    per-cell bound an fp32-accumulating kernel must stay inside:
+    D * 2^-22 * sum_i |q_i| |x_i|. At most D additions, each rounding or
+    truncating by at most 2^-23 relative to a partial sum that
+    sum |q_i||x_i| bounds, times 2 for the undocumented alignment inside
+    the 128-wide MFMA add. A derived worst case, not a measured figure."""
+    D = q.shape[1]
+    ref = q @ x.T
+    bound = (q.abs() @ x.abs().T) * (D * 2.0 ** -22)
+    return ref, bound
+
+
+def reference_fp4x4_scores(Q4: torch.Tensor, QS: torch.Tensor, X4: torch.Tensor,
+                           XS: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """What an fp4 x fp4 scan score is supposed to be: (ref, bound), both
+    fp64 [nq, nx] (reference_scores_bound of the decoded operands). Q and X
+    are stored in the same fragment order, so no permutation is needed."""
+    return reference_scores_bound(reference_fp4_decode(Q4, QS),
+                                  reference_fp4_decode(X4, XS))
+
+
 def quantize_fp4_mx(
     x: torch.Tensor,
     out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
@@ -864,19 +917,8 @@ def overflow_rescan_plan(
 def fp4x4_rescan(Q4, QS, X4, theta2, rows, cap, owner=None, qowner=None, n_swaths=0):
     """Scan the query rows `rows` (int64 [n]) of Q4 / QS again, at
     theta2[rows], with the plain v10 scan (the owned scan with owners).
-    Returns (cand_scores, cand_ids, counts) of those n rows.
-
-    Scan scores do not depend on which queries share a block, with one
-    exception: the scans stage the query scale sheet in 16 B pieces and
-    clamp the last piece into the array, so when nq * D/32 is not a multiple
-    of 16 the last rows are scored with their neighbours' scales (the clamp
-    rule noted in docs/NOTES-NEXT.md; D = 512 and 1024 are never affected).
-    The gathered block is therefore padded to a multiple of 4 rows, by
-    repeating the last row, and the padding dropped from the result."""
-    n = int(rows.numel())
-    pad = (-n) % 4
-    if pad:
-        rows = torch.cat([rows, rows[-1:].expand(pad)])
+    Returns (cand_scores, cand_ids, counts) of those n rows. Scan scores
+    do not depend on which queries share a block."""
     q4r, qsr = Q4[rows].contiguous(), QS[rows].contiguous()
     th2 = theta2[rows].contiguous()
     if owner is None:
@@ -884,7 +926,7 @@ def fp4x4_rescan(Q4, QS, X4, theta2, rows, cap, owner=None, qowner=None, n_swath
     else:
         out = ext().topk_scan_threshold_fp4x4_owned(
             q4r, qsr, X4[0], X4[1], th2, owner, qowner[rows].contiguous(), cap, n_swaths)
-    return tuple(t[:n] for t in out)
+    return tuple(out)
 
 
 def _scan_fp4x4_rescan(Q, Q4, QS, X4, theta, cap, x_norm_bound, owner, qowner, need):
